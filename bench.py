@@ -9,7 +9,7 @@ evaluated on the device after every sweep exactly as in production.  Every point
 counted in `value`, masked (land) points included; `value_active` and every roofline fraction count
 only the tiles the kernel actually ran.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--sweeps S] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--sweeps S] [--dump-outputs DIR] ...
 
 --gpus N > 1 started WITHOUT a torchrun environment launches its own N ranks (torch.distributed.run,
 rendezvous on 127.0.0.1) and fails loudly when fewer than N GPUs are visible; started under torchrun it
@@ -43,6 +43,9 @@ Extra objects in the ONE JSON line rank 0 prints (N = 1, c2):
                  (the N = 1 rate for the same per-GPU work); flags_sha256: digest of the gathered per-slice flags.
   parity         the timed solve repeated from the initial state and compared BIT FOR BIT with the oracle.
   cpu_baseline   the oracle's lexicographic sweep (the reference's execution model), -march=native build.
+
+--dump-outputs DIR: after the timed steps, what the last of them handed back is written to DIR as float64 .npy files (see
+dump_outputs), so that two builds can be compared output for output: the inputs are seeded, the same for the same arguments.
 """
 import argparse
 import json
@@ -104,7 +107,12 @@ def parse():
     ap.add_argument('--sustained-seconds', type=float, default=5.0)
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--parity-sweeps', type=int, default=0, help='sweeps of the parity check (0 = the timed count)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write the outputs of the last timed step to DIR/<name>.npy (at most 64 MB in all)')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 # ------------------------------------------------------------------ the oracle (checker / CPU baseline only)
@@ -322,6 +330,31 @@ def c5_members(lo, hi, shape=(50, 360, 720)):
     p['coefs'] = [c if k in p['shared'] else np.concatenate([q['coefs'][k] for q in parts])
                   for k, c in enumerate(p['coefs'])]
     return p
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, S, flags, rank, world):
+    """--dump-outputs: the outputs of the last timed step as float64 .npy files in `d`.
+      flags.npy                 [members_total, 3]: the per-slice flags gathered over the ranks (rank 0 writes it)
+      S.npy                     [members, *grid]: the final field of every member this rank solved (S_rank<r>.npy for N > 1)
+    When a rank's S does not fit in its share of DUMP_BYTES (N > 1: one N-th of it), a fixed sample of its points is
+    written instead: S_sample.npy holds the values at the flat indices in S_sample_index.npy, drawn with a fixed seed."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    flags = np.ascontiguousarray(flags, dtype=np.float64)
+    if rank == 0:
+        np.save(os.path.join(d, 'flags.npy'), flags)
+    sfx = '' if world == 1 else '_rank%d' % rank
+    budget = (DUMP_BYTES - flags.nbytes - 4096) // world             # (4096: the .npy headers)
+    if S.numel() * 8 <= budget:
+        np.save(os.path.join(d, 'S%s.npy' % sfx), S.cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(12345).integers(0, S.numel(), budget // 16))
+    vals = S.reshape(-1)[torch.from_numpy(idx).to(S.device)].cpu().numpy()
+    np.save(os.path.join(d, 'S%s_sample.npy' % sfx), vals)
+    np.save(os.path.join(d, 'S%s_sample_index.npy' % sfx), idx.astype(np.float64))
 
 
 def time_resident(rp, sweeps, steps, warmup, **opts):
@@ -739,6 +772,8 @@ def main():
     # grouping follows the launch's tiling -- 1e-12 between two splits of a batch, DESIGN 5.3 -- and is not hashed.)
     ck = rp.S.view(torch.int64).reshape(nb, -1).sum(dim=1).cpu().numpy().reshape(nb, 1)
     all_ck = xdist.gather_blocks(ck, total_members) if joined else ck
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rp.S, allf, rank, world)
     if joined:
         backend = torch.distributed.get_backend()
         tdev = dev if backend == 'nccl' else torch.device('cpu')

@@ -20,6 +20,8 @@ Fixtures written
   eliassen.npz      real data for the 9-point form: Data/ZonalMean.nc (Hadley) and Data/TC2D.nc (TC)
                     coefficients + forcing, S and flags from the reference kernel
   mjo_ol.npz        real data: Data/MJO.nc `ol` (73x144 f32) for the Gill-Matsuno real case
+  live_reference.npz  S and flags of the reference on tests/test_oracle_live_reference.py's cases()
+                    (inputs regenerated there from the seed)
 """
 import os
 import subprocess
@@ -366,8 +368,21 @@ def gen3d_cases():
     print('gen3d_cases: %d cases' % cid)
 
 
+def live_cases():
+    """tests/test_oracle_live_reference.py's seeded cases through the reference kernels: outputs only."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_oracle_live_reference import REF_NAMES, cases
+    out = {}
+    for i, (kernel, S0, arrays, args, mxLoop, tol) in enumerate(cases()):
+        S = S0.copy(); fl = np.array([0., 1., 0.])
+        getattr(ref, REF_NAMES[kernel])(S, *arrays, *args, fl, mxLoop, tol)
+        out['S%03d' % i] = S; out['f%03d' % i] = fl
+    np.savez_compressed(os.path.join(HERE, 'live_reference.npz'), **out)
+    print('live_reference: %d cases' % (len(out) // 2))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['small', 'bih', 'std2dt', 'gen3d', 'real', 'eliassen', 'gm', 'stommel']
+    which = sys.argv[1:] or ['small', 'bih', 'std2dt', 'gen3d', 'real', 'eliassen', 'gm', 'stommel', 'live']
     if 'bih' in which: bih_cases()
     if 'std2dt' in which: std2dt_cases()
     if 'gen3d' in which: gen3d_cases()
@@ -376,3 +391,4 @@ if __name__ == '__main__':
     if 'eliassen' in which: eliassen()
     if 'gm' in which: gill_matsuno()
     if 'stommel' in which: stommel()
+    if 'live' in which: live_cases()

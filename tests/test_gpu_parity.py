@@ -45,6 +45,17 @@ BCS = [('fixed', 'fixed'), ('fixed', 'periodic'), ('extend', 'fixed'), ('extend'
        ('fixed', 'extend')]
 
 
+def assert_short_odd_seam_takes_colour_launches(p, nsw, tol, So, flo, colours, what, **kw):
+    """Periodic x with an odd xc below 64 columns has no fused kernel (xinv_plan.h: the seam variants need xc >= 64):
+    asking for the fused path is an argument error, and the default path runs the colour launches with the seam
+    colours -- bit for bit the oracle.  (Longer odd rows on the fused kernels: test_gpu_seam.py.)"""
+    with pytest.raises(Exception, match='no fused kernel'):
+        run_hip_batched([p], nsw, tol, path=PATH_FUSED, **kw)
+    S, fl, st = run_hip_batched([p], nsw, tol)
+    assert st['path'] == PATH_COLOUR and st['colours'] == colours, st
+    assert_same(S[0], fl[0], So, flo, what)
+
+
 @pytest.mark.parametrize('kind', ['std2d', 'gen2d'])
 @pytest.mark.parametrize('BCy,BCx', BCS)
 @pytest.mark.parametrize('bnz', [0, 1])
@@ -145,12 +156,13 @@ def _uniform3d(p, rng):
 @pytest.mark.parametrize('nw', [8, 12, 16])
 @pytest.mark.parametrize('shape', [(6, 9, 12), (5, 30, 130), (9, 21, 260), (4, 14, 11), (3, 3, 3)])
 def test_fused_path_3d(BCy, BCx, msk, uni, nw, shape):
-    if BCx == 'periodic' and shape[2] % 2:
-        pytest.skip('odd-xc periodic seam on rows shorter than 64 columns goes through the colour path (longer rows: test_gpu_seam.py)')
     p = rand3d(shape[0], shape[1], shape[2], BCy, BCx, msk, seed=_seed((BCy, BCx, msk, uni, shape)))
     if uni:
         p = _uniform3d(p, None)
     So, flo = run_oracle(p, 12, 1e-9, COLOUR_2)
+    if BCx == 'periodic' and shape[2] % 2:                  # (every odd width here is below 64)
+        assert_short_odd_seam_takes_colour_launches(p, 12, 1e-9, So, flo, 4, 'colour 3d %r' % (shape,), rows_per_tile=nw)
+        return
     S, fl, st = run_hip_batched([p], 12, 1e-9, path=PATH_FUSED, rows_per_tile=nw)
     # (sixteen wavefronts = 128 VGPRs per lane: only the x-uniform variant without 'extend' fits; the others get twelve)
     nw_ran = 12 if (nw == 16 and not (uni and BCy != 'extend')) else nw
@@ -198,10 +210,12 @@ FUSED_SHAPES = [(17, 24), (12, 20), (40, 300), (70, 130), (33, 257), (8, 4), (3,
 @pytest.mark.parametrize('K', [1, 2, 3, 4])
 def test_fused_path(kind, BCy, BCx, msk, shape, K):
     yc, xc = shape
-    if BCx == 'periodic' and xc % 2 and xc < 64:
-        pytest.skip('odd-xc periodic seam on rows shorter than 64 columns goes through the colour path (covered there)')
     p = rand2d(kind, yc, xc, BCy, BCx, 0, msk, seed=_seed((kind, BCy, BCx, msk, shape)))
     So, flo = run_oracle(p, 24, 1e-9, COLOUR_2)
+    if BCx == 'periodic' and xc % 2 and xc < 64:
+        assert_short_odd_seam_takes_colour_launches(p, 24, 1e-9, So, flo, 4, 'colour %s %r' % (kind, shape),
+                                                    sweeps_per_launch=K, rows_per_tile=16)
+        return
     S, fl, st = run_hip_batched([p], 24, 1e-9, path=PATH_FUSED, sweeps_per_launch=K, rows_per_tile=16)
     # the general form has K = 1, 2, 3; the standard form also 4
     assert st['path'] == PATH_FUSED and st['sweeps_per_launch'] == (K if kind == 'std2d' else min(K, 3))
@@ -241,10 +255,12 @@ def test_fused_standard_three_and_four_sweeps_per_pass(BCy, BCx, msk, shape, K, 
     """K = 3, 4 (standard form with per-row A, C): same ordering, so bit for bit the oracle;
     nsw + 1 sweeps leave a tail of 1 (25 = 6x4 + 1 = 8x3 + 1) or 3 / 2 (23) for a shorter last pass."""
     yc, xc = shape
-    if BCx == 'periodic' and xc % 2 and xc < 64:
-        pytest.skip('odd-xc periodic seam on rows shorter than 64 columns goes through the colour path (covered there)')
     p = _uniform2d(rand2d('std2d', yc, xc, BCy, BCx, 0, msk, seed=_seed(('k34', BCy, BCx, msk, shape))))
     So, flo = run_oracle(p, nsw, 1e-9, COLOUR_2)
+    if BCx == 'periodic' and xc % 2 and xc < 64:
+        assert_short_odd_seam_takes_colour_launches(p, nsw, 1e-9, So, flo, 4, 'colour K=%d %r' % (K, shape),
+                                                    sweeps_per_launch=K, rows_per_tile=16)
+        return
     for rows in (16, 0):
         S, fl, st = run_hip_batched([p], nsw, 1e-9, path=PATH_FUSED, sweeps_per_launch=K, rows_per_tile=rows)
         assert st['path'] == PATH_FUSED and st['sweeps_per_launch'] == K, st
@@ -818,14 +834,18 @@ NINE_SHAPES = [(17, 24), (12, 20), (40, 300), (33, 257), (9, 8), (3, 3), (50, 51
 @pytest.mark.parametrize('shape', NINE_SHAPES)
 def test_fused_nine_point(kind, K, BCy, BCx, msk, shape):
     """B != 0: the fused 4-colour kernel against the oracle's 4-colour ordering (incl. the
-    reference's west-periodic operands of invert_standard_2D)."""
+    reference's west-periodic operands of invert_standard_2D); odd xc with periodic x adds the seam
+    colours c0' / c2' (k_fused9's SEAM variants from 64 columns, the colour launches below)."""
     yc, xc = shape
-    if BCx == 'periodic' and xc % 2:
-        pytest.skip('odd-xc periodic seam goes through the colour path')
+    seam = BCx == 'periodic' and xc % 2 == 1
     p = rand2d(kind, yc, xc, BCy, BCx, 1, msk, seed=_seed((kind, BCy, BCx, msk, shape, 9)), omega=1.1)
     So, flo = run_oracle(p, 17, 1e-9, COLOUR_AUTO)
+    if seam and xc < 64:
+        assert_short_odd_seam_takes_colour_launches(p, 17, 1e-9, So, flo, 6, 'colour 9-point %s %r' % (kind, shape),
+                                                    sweeps_per_launch=K, rows_per_tile=10)
+        return
     S, fl, st = run_hip_batched([p], 17, 1e-9, path=PATH_FUSED, sweeps_per_launch=K, rows_per_tile=10)
-    assert st['path'] == PATH_FUSED and st['colours'] == 4 and st['sweeps_per_launch'] == K
+    assert st['path'] == PATH_FUSED and st['colours'] == (6 if seam else 4) and st['sweeps_per_launch'] == K, st
     assert_same(S[0], fl[0], So, flo, 'fused 9-point K=%d %s %r' % (K, kind, shape))
 
 
