@@ -294,12 +294,14 @@ def test_plan_solve_frames_equals_repeated_solves(kind, mxLoop, tol, nf):
     ref = ResidentProblem(p, null_zero_B=True)
     ref_frames, ref_flags = [], []
     for f in range(nf):
-        fl, st = ref.solve(mxLoop, tol)
+        fl, ref_st = ref.solve(mxLoop, tol)
         ref_frames.append(ref.S.clone()); ref_flags.append(np.array(fl, copy=True))
     rp = ResidentProblem(p, null_zero_B=True)
     frames = torch.empty((nf,) + tuple(rp.S.shape), dtype=rp.S.dtype, device=rp.S.device)
     fl, st = rp.solve_frames(frames, mxLoop, tol)
     assert fl.shape == (nf, rp.nb, 3)
+    keys = ('point_factor', 'k_chunks', 'cut_tiles', 'pipelined', 'masked_tile_ppm')
+    assert {k: st[k] for k in keys} == {k: ref_st[k] for k in keys}, (st, ref_st)
     for f in range(nf):
         assert torch.equal(frames[f], ref_frames[f]), 'frame %d differs' % f
         assert np.array_equal(fl[f][:, [0, 2]], ref_flags[f][:, [0, 2]]), (f, fl[f], ref_flags[f])

@@ -438,13 +438,7 @@ static int solve_host_one(Problem &p, double *flags, const xinv_options &opt, co
         if (nchunk > 1 && p.kind != KIND_BIH2D)
             for (Workspace *w : wss) {
                 if ((rc = ensure_dev(&w->S2, &w->S2_cap, (size_t)mmax * n * sizeof(double)))) return rc;
-                if ((rc = ensure_dev(&w->ctl, &w->ctl_cap, (size_t)mmax * sizeof(XinvCtl)))) return rc;
-                if (w->hctl_cap < (size_t)mmax) {
-                    if (w->hctl) HIPCHK(hipHostFree(w->hctl));
-                    w->hctl = nullptr; w->hctl_cap = 0;
-                    HIPCHK(hipHostMalloc((void **)&w->hctl, 2 * (size_t)mmax * sizeof(XinvCtl), XINV_HOST_COHERENT));
-                    w->hctl_cap = (size_t)mmax;
-                }
+                if ((rc = ensure_dev(&w->ctl, &w->ctl_cap, (size_t)mmax * sizeof(XinvCtl))) || (rc = ensure_mirror(w, mmax))) return rc;
             }
     }
     xinv_stats acc;
@@ -578,21 +572,8 @@ static int solve_host_one(Problem &p, double *flags, const xinv_options &opt, co
         if (pl.path != XINV_PATH_FUSED || pl.skip || pl.pq) return roll2d ? ROLL_FALLBACK : (t_err = "internal: rolling batch without a streaming kernel", XINV_ERR_HIP);
         const double plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan0).count();
         // workspace (run_sweeps' own, without the lagged norm: never in 3-D)
-        r = tail_wait(ws, scp);
-        if (r) return r;
-        if ((r = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)nb * sizeof(XinvCtl)))) return r;
-        if (ws->hctl_cap < (size_t)nb) {
-            if (ws->hctl) HIPCHK(hipHostFree(ws->hctl));
-            ws->hctl = nullptr; ws->hctl_cap = 0;
-            HIPCHK(hipHostMalloc((void **)&ws->hctl, 2 * (size_t)nb * sizeof(XinvCtl), XINV_HOST_COHERENT));
-            ws->hctl_cap = (size_t)nb;
-        }
-        const size_t pbytes = (partial_bytes(d, pl) + 255) & ~(size_t)255;
-        ws->partials_half = pbytes;
-        if ((r = ensure_dev(&ws->partials, &ws->partials_cap, pbytes))) return r;
-        if ((r = ensure_dev(&ws->S2, &ws->S2_cap, (size_t)nb * n * sizeof(double)))) return r;
-        hipLaunchKernelGGL(k_solve_init, dim3((unsigned)std::max<int64_t>(cdiv(nb, 256), std::min<int64_t>(256, cdiv((int64_t)(pbytes / 16), 256)))),
-                           dim3(256), 0, scp, ws->ctl, nb, (uint4 *)ws->partials, (int64_t)(pbytes / 16));
+        if ((r = solve_workspace(ws, scp, nb, true, partial_bytes(d, pl), false, nb * n, false))) return r;
+        solve_init(ws, scp, nb, ws->partials_half);
         double *buf[2] = { d.S, ws->S2 };
         const int64_t max_sweeps = d.stop.mxLoop + 1;
         const int Kf = pl.K;
@@ -622,24 +603,17 @@ static int solve_host_one(Problem &p, double *flags, const xinv_options &opt, co
                 const XinvCtl &c = hc[m];
                 if (!c.done) { t_err = "internal: rolling batch: a member retired before its stop rule fired"; return XINV_ERR_HIP; }
                 if (c.overflow == 2) { t_err = "internal: norm partials of a sweep launch never arrived (watchdog) in the rolling batch"; return XINV_ERR_HIP; }
-                const int64_t sw = c.sweeps;
-                const int64_t rl = (sw - 1) / Kf;                   // the member's launch that holds sweep sw (0-based)
-                const int64_t lend = std::min<int64_t>((rl + 1) * Kf, max_sweeps);
-                int where;
-                if (sw == lend) where = (int)((join[(size_t)m] + rl + 1) & 1);
-                else {                                              // stopped inside a pass: redo from its source, sweep by sweep
-                    int cur = (int)((join[(size_t)m] + rl) & 1);
-                    for (int64_t q = rl * Kf; q < sw; q++) {
-                        int rr = launch_planned(d, pl, ws, g.s, 1, buf[cur], buf[cur ^ 1], m, 1, 1, 1);
-                        if (rr) return rr;
-                        cur ^= 1;
-                    }
-                    where = cur;
+                // (the member's launch rl that holds sweep sw ping-pongs from the buffer of its join's parity)
+                const int64_t sw = c.sweeps, rl = (sw - 1) / Kf;
+                const int src = xinv_pingpong_src(join[(size_t)m], rl);
+                const XinvFinal w = xinv_final_in(rl * Kf, std::min<int64_t>((rl + 1) * Kf, max_sweeps), src, src ^ 1, 2, false, sw);
+                for (int64_t q = 0; q < w.redo; q++) {              // stopped inside a pass: redo from its source, sweep by sweep
+                    int rr = launch_planned(d, pl, ws, g.s, 1, buf[xinv_redo_read(w.r, q)], buf[xinv_redo_write(w.r, q)], m, 1, 1, 1);
+                    if (rr) return rr;
                 }
-                if (where != 0)
+                if (w.where != 0)
                     HIPCHK(hipMemcpyAsync(d.S + m * n, ws->S2 + m * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g.s));
-                if (c.overflow) flags[3 * m + 0] = 1.0;
-                if (c.wrote) { flags[3 * m + 1] = c.flag1; flags[3 * m + 2] = c.flag2; }
+                member_flags(c, flags + 3 * m);
                 sweeps_max = std::max<int64_t>(sweeps_max, sw);
             }
             hipEvent_t after;
@@ -744,11 +718,8 @@ static int solve_host_one(Problem &p, double *flags, const xinv_options &opt, co
         HIPCHK(hipStreamSynchronize(scp));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ev_t0, ev_t1));
-        t_stats.path = pl.path; t_stats.colours = pl.ncol; t_stats.sweeps_per_launch = Kf; t_stats.rows_per_tile = pl.RY;
-        t_stats.xuniform_mask = (int32_t)pl.um; t_stats.lanes = nl; t_stats.sweep_launches = nlaunch;
-        t_stats.sweeps_max = sweeps_max; t_stats.sweep_ms = ms; t_stats.plan_ms = plan_ms;
-        t_stats.k_chunks = pl.K2 ? std::max(1, pl.nkc2) : 0;
-        t_stats.pipelined = pl.pipe ? pl.npair : 0;
+        plan_stats(d, pl, nl, 0);                                    // (a launch covers the members in flight: no count of cut tiles)
+        t_stats.sweep_launches = nlaunch; t_stats.sweeps_max = sweeps_max; t_stats.sweep_ms = ms; t_stats.plan_ms = plan_ms;
         t_stats.rolling = 1;
         acc = t_stats; acc_set = true;
         return XINV_OK;

@@ -1,18 +1,18 @@
-// xinv_sweep.h -- the sweep loop of libxinv_hip.so: launch chains with pipelined polling of the device-side stop
-// flags, lanes, the lagged norm and its three-buffer rotation, watchdog recovery, finalise() (where each member's
-// final state lives; the redo of a pass the stop rule fired in), the device-pointer solve and the resident plans
-// (xinv_plan_*).  Included by xinv_hip.hip only, after xinv_plan.h.
+// xinv_sweep.h -- the sweep loop of libxinv_hip.so: the solve workspace, launch chains with pipelined polling of the
+// device-side stop flags, lanes, the lagged norm and its three-buffer rotation (xinv_rotation.h), watchdog recovery,
+// finalise() (where each member's final state lives; the redo of a pass the stop rule fired inside), the device-pointer
+// solve and the resident plans (xinv_plan_*).  Included by xinv_hip.hip only, after xinv_plan.h.
 #pragma once
+#include "xinv_rotation.h"
 
 // ------------------------------------------------------------------ the sweep loop
 // What the loop leaves for finalise(): where each launch started, the final control blocks.
 struct SweepRun {
-    double *S2 = nullptr;
-    double *buf[3] = {nullptr, nullptr, nullptr};
+    double *buf[3] = {nullptr, nullptr, nullptr};        // S, S2, S3
     int nbuf = 2;                                        // 3 with the lagged norm
-    std::vector<signed char> srcb, dstb;                 // launch i swept buf[srcb[i]] into buf[dstb[i]] (see launch_idx)
+    std::vector<signed char> srcb, dstb;                 // launch i swept buf[srcb[i]] into buf[dstb[i]] (xinv_rot_dst)
     bool lag = false;
-    std::vector<int64_t> bound;                          // bound[i] = sweeps before launch i (fused path)
+    std::vector<int64_t> bound;                          // bound[i] = sweeps before launch i, bound[#launches] = launched (fused path)
     int64_t launched = 0, nlaunch = 0;
     double ms_total = 0.0;
     const XinvCtl *hc = nullptr;                         // the slot holding the final control blocks
@@ -80,7 +80,6 @@ static int lane_rule(const Problem &p, double est_pass_us)
     return 2;
 }
 
-// workspace, then chunks of launches with pipelined polling of the device-side stop flags
 // bytes of the norm partials of one solve (every member, every tiling its launches may use)
 static size_t partial_bytes(const Problem &p, const Plan &pl)
 {
@@ -93,31 +92,85 @@ static size_t partial_bytes(const Problem &p, const Plan &pl)
     return (size_t)p.nbatch * XINV_NORM_BLOCKS * (sizeof(double) + sizeof(long long));
 }
 
-static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt, Workspace *ws, hipStream_t st,
-                      SweepRun &R)
+// ------------------------------------------------------------------ the solve workspace (every sweep loop)
+// the pinned mirror of `nctl` control blocks for the host's polls: two slots, polling is pipelined
+static int ensure_mirror(Workspace *ws, int64_t nctl)
 {
-    const int64_t n = p.zc * p.yc * p.xc;
-    int rc = XINV_OK;
-    (void)n; (void)rc;
-    // ---- workspace ---------------------------------------------------------------------------
-    rc = tail_wait(ws, st);                              // (the previous plan solve's copy into its caller's S reads S2 / S3)
-    if (rc) return rc;
-    rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)p.nbatch * sizeof(XinvCtl));
-    if (rc) return rc;
-    if (ws->hctl_cap < (size_t)p.nbatch) {             // two slots: polling is pipelined
-        if (ws->hctl) HIPCHK(hipHostFree(ws->hctl));
-        HIPCHK(hipHostMalloc((void **)&ws->hctl, 2 * (size_t)p.nbatch * sizeof(XinvCtl), XINV_HOST_COHERENT));
-        ws->hctl_cap = (size_t)p.nbatch;
+    if (ws->hctl_cap >= (size_t)nctl) return XINV_OK;
+    if (ws->hctl) HIPCHK(hipHostFree(ws->hctl));
+    ws->hctl = nullptr; ws->hctl_cap = 0;
+    HIPCHK(hipHostMalloc((void **)&ws->hctl, 2 * (size_t)nctl * sizeof(XinvCtl), XINV_HOST_COHERENT));
+    ws->hctl_cap = (size_t)nctl;
+    return XINV_OK;
+}
+
+// Behind the previous plan solve's tail (its copy into its caller's S reads S2 / S3): control blocks of `nctl` members
+// (with their pinned mirror when `mirror`), the norm partials
+// (`pbytes`, rounded up to 256 bytes: ws->partials_half; twice that with `two_halves`, the lagged norm's two parities) and
+// the twins of S, `span` elements each: S2 (span > 0) and S3.
+static int solve_workspace(Workspace *ws, hipStream_t st, int64_t nctl, bool mirror, size_t pbytes, bool two_halves,
+                           int64_t span, bool s3)
+{
+    int rc;
+    if ((rc = tail_wait(ws, st)) || (rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)nctl * sizeof(XinvCtl)))) return rc;
+    if (mirror && (rc = ensure_mirror(ws, nctl))) return rc;
+    ws->partials_half = (pbytes + 255) & ~(size_t)255;
+    if ((rc = ensure_dev(&ws->partials, &ws->partials_cap, (two_halves ? 2 : 1) * ws->partials_half))) return rc;
+    if (span > 0 && (rc = ensure_dev(&ws->S2, &ws->S2_cap, (size_t)span * sizeof(double)))) return rc;
+    if (s3 && (rc = ensure_dev(&ws->S3, &ws->S3_cap, (size_t)span * sizeof(double)))) return rc;
+    return XINV_OK;
+}
+
+// Control blocks ws->ctl[0, nctl) reset and the first `clear` bytes of the partials zeroed (tagged partials: no stale
+// sequence numbers) in ONE launch: a dispatch less on the way to the first sweep launch.  (Measured and not kept: the NEXT
+// solve's initialisation queued behind a plan solve -- the sweep launch waits for it either way.)
+static void solve_init(Workspace *ws, hipStream_t st, int64_t nctl, size_t clear)
+{
+    hipLaunchKernelGGL(k_solve_init, dim3((unsigned)std::max<int64_t>(cdiv(nctl, 256), std::min<int64_t>(256, cdiv((int64_t)(clear / 16), 256)))),
+                       dim3(256), 0, st, ws->ctl, nctl, (uint4 *)ws->partials, (int64_t)(clear / 16));
+}
+
+// A member's flags [overflow, flag1, flag2] from its final control block (flag1 / flag2 once written).
+static inline void member_flags(const XinvCtl &c, double *fl)
+{
+    if (c.overflow) fl[0] = 1.0;
+    if (c.wrote) { fl[1] = c.flag1; fl[2] = c.flag2; }
+}
+
+// What a solve's stats say about its plan: `lanes` launch chains, each launch of the first chain covering
+// `launch_members` members (0: a changing set -- no count of cut tiles).
+static void plan_stats(const Problem &p, const Plan &pl, int lanes, int64_t launch_members)
+{
+    const bool fused = pl.path == XINV_PATH_FUSED;
+    t_stats.path = pl.path;
+    t_stats.colours = pl.ncol;
+    t_stats.sweeps_per_launch = fused ? pl.K : 1;
+    t_stats.rows_per_tile = pl.RY;
+    t_stats.xuniform_mask = (fused || p.kind == KIND_BIH2D) ? (int32_t)pl.um : 0;
+    t_stats.masked_tile_pct = (fused && pl.skip) ? pl.skip_pct : 0;
+    t_stats.masked_tile_ppm = (fused && pl.skip) ? pl.skip_ppm : 0;
+    t_stats.pipelined = (fused && pl.pipe) ? pl.npair : 0;
+    t_stats.lanes = lanes;
+    t_stats.point_factor = (fused && pl.pq) ? (pl.alias_ac ? 2 : 1) : 0;
+    if (fused && p.kind == KIND_BIH2D) t_stats.point_factor = pl.bih_vm;
+    if (fused && p.kind == KIND_STD3D && pl.K2) {
+        t_stats.k_chunks = std::max(1, pl.nkc2);
+        const int64_t tiles = (int64_t)pl.nsg2 * pl.nrb2 * launch_members;
+        if (launch_members > 0)
+            t_stats.cut_tiles = (int32_t)(tiles - p3_whole_tiles(tiles, std::max(1, pl.nkc2), pl.KC2, p.zc, pl.cus));
     }
-    size_t pbytes = partial_bytes(p, pl);
-    // Lagged norm (5-point 2-D kernels): the sweep kernel only publishes its partials; an extra workgroup
-    // of the NEXT launch adds them and applies the stop rule while that pass's tiles run.  Measured at
-    // 3600x1800, K = 4 (profiles/r02_norm_lag_experiment.txt): 47.6 us per launch with the in-kernel
-    // reducer (a global round trip after the last tile), 43.7 us publishing only, 41.7 us without any
-    // norm; a reducer kernel on a second stream (events both ways) was slower than either: 50.6 us.
-    // The decision about pass i arrives while pass i+1 runs, so S rotates through THREE buffers: pass
-    // i+2 -- the first that could overwrite the source of pass i -- starts after reducer i has finished,
-    // finds the member stopped and does nothing, and finalise() re-sweeps from the intact source.
+}
+
+// ------------------------------------------------------------------ run_sweeps' steps
+// Lagged norm (5-point 2-D kernels): the sweep kernel only publishes its partials; an extra workgroup of the NEXT launch
+// adds them and applies the stop rule while that pass's tiles run.  Measured at 3600x1800, K = 4
+// (profiles/r02_norm_lag_experiment.txt): 47.6 us per launch with the in-kernel reducer (a global round trip after the
+// last tile), 43.7 us publishing only, 41.7 us without any norm; a reducer kernel on a second stream (events both ways) was
+// slower than either: 50.6 us.  The decision about pass i arrives while pass i+1 runs, so S rotates through THREE buffers
+// (xinv_rotation.h): pass i+2 -- the first that could overwrite the source of pass i -- starts after reducer i has
+// finished, finds the member stopped and does nothing, and finalise() re-sweeps from the intact source.
+static bool lag_candidate(const Problem &p, const Plan &pl, const xinv_options &opt)
+{
     const bool lag_env = opt.norm_lag ? opt.norm_lag > 0 : XINV_ENV_INT("XINV_LAG", 1) != 0;
     // Only where a member has many workgroups: the reducing workgroup is one more per member and launch,
     // and with one or two tile workgroups per member (365 slices of 73x144) it would double the launch.
@@ -128,116 +181,186 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
     const int64_t wg_member = pl.skip ? pl.ntl / tpw : (int64_t)cdiv((int64_t)cdiv(p.xc, own_cols) * pl.nrb, tpw);
     // ... and only where a launch is one or two rounds of workgroups: with many rounds (64 Gill-Matsuno
     // members: 3.97e11 without, 3.73e11 with) the in-kernel reducer's wait already hides behind other tiles.
-    const bool lag_cand = lag_env && pl.path == XINV_PATH_FUSED && wg_member >= 32 &&
-                          wg_member * p.nbatch <= 1024 && !is3d(p.kind);     // every 2-D streaming kernel
-    pbytes = (pbytes + 255) & ~(size_t)255;
-    ws->partials_half = pbytes;
-    rc = ensure_dev(&ws->partials, &ws->partials_cap, lag_cand ? 2 * pbytes : pbytes);
-    if (rc) return rc;
-    const size_t pclear = (pl.path == XINV_PATH_FUSED) ? (lag_cand ? 2 * pbytes : pbytes) : 0;   // tagged partials: no stale sequence numbers
-    double *&S2 = R.S2;
-    if (pl.path == XINV_PATH_COLOUR && p.kind == KIND_BIH2D) {       // side buffer of the row-class kernel
-        rc = ensure_dev(&ws->S2, &ws->S2_cap, (size_t)((p.nbatch - 1) * p.sS + n) * sizeof(double));
-        if (rc) return rc;
-    }
-    if (pl.path == XINV_PATH_FUSED) {
-        const size_t need = (size_t)((p.nbatch - 1) * p.sS + n) * sizeof(double);
-        rc = ensure_dev(&ws->S2, &ws->S2_cap, need);
-        if (rc) return rc;
-        S2 = ws->S2;
-    }
+    return lag_env && pl.path == XINV_PATH_FUSED && wg_member >= 32 &&
+           wg_member * p.nbatch <= 1024 && !is3d(p.kind);     // every 2-D streaming kernel
+}
 
-    // (control blocks and partials in ONE launch: a dispatch less on the way to the first sweep launch.  Measured and not
-    //  kept: the NEXT solve's initialisation queued behind a plan solve -- the sweep launch waits for it either way)
-    hipLaunchKernelGGL(k_solve_init, dim3((unsigned)std::max<int64_t>(cdiv(p.nbatch, 256), std::min<int64_t>(256, cdiv((int64_t)(pclear / 16), 256)))),
-                       dim3(256), 0, st, ws->ctl, p.nbatch, (uint4 *)ws->partials, (int64_t)(pclear / 16));
+// Launches per chunk: a chunk = `check_every` launches followed by an asynchronous copy of the control blocks.
+static int poll_every(const Problem &p, const Plan &pl, const xinv_options &opt, double est_pass_us)
+{
+    if (opt.check_every > 0) return opt.check_every;
+    // poll the device stop flags about every 2 ms of sweeping (fused kernels run at roughly
+    // 2e5 points per microsecond, the colour path at a quarter of that); launches issued after
+    // a member has stopped are no-ops of a few microseconds each
+    // (round 3: the pipelined 2-D pass runs at 6-7e5 points per microsecond; with the round-1 constant a 500-sweep
+    //  solve at 3600x1800 was polled 18 times -- each poll ends a chunk: one-workgroup norm reduction of the lagged
+    //  launch + control-block copy, ~10 us of idle GPU -- 4 % of the solve)
+    const double est_us = std::max(4.0, est_pass_us);
+    // (a non-positive tolerance can never stop a solve -- the reference tests' idiom for a fixed number of sweeps,
+    //  tests/test_GeoAdjustment.py:31 -- only an overflow or, in the standard form, a zero norm can: nothing worth a
+    //  poll every 2 ms, each of which holds the next launch back for ~10 us)
+    if (p.stop.tolerance <= 0.0 && pl.path == XINV_PATH_FUSED) return 256;
+    return (int)std::min(256.0, std::max(4.0, 2000.0 / est_us));
+}
 
-    // ---- sweep loop ----------------------------------------------------------------------------
+// Small problems are bound by the host's launch rate (a 151x251 coloured sweep is six launches of 2-3 us each): a full
+// chunk is captured once into a hipGraph on an engine-owned stream and replayed into the caller's stream (R.graph_exec).
+// The chunk has an even number of launches, so the ping-pong parity at its start is always 0.  A failed capture leaves
+// plain launches.
+static int capture_chunk(const Problem &p, const Plan &pl, const xinv_options &opt, Workspace *ws, SweepRun &R,
+                         int64_t max_sweeps, int &check_every)
+{
+    const int graph_env = opt.graph ? (opt.graph > 0 ? 1 : 0) : XINV_ENV_INT("XINV_GRAPH", -1);
+    const double est_launch_us = (double)p.nbatch * (double)(p.zc * p.yc * p.xc) * R.Kf /
+                                 ((pl.path == XINV_PATH_FUSED) ? 2.0e5 : 4.0e4);
+    // Replay pays on the colour path only (six or more tiny launches per sweep: 25.8 -> 22.2 us per sweep
+    // at 151x251); for the fused kernels it gained nothing (round 1; C1: 2.5 ms replayed against 1.9 ms
+    // per 500 sweeps with plain launches and the lagged norm, which excludes replay).  XINV_GRAPH=1 forces it.
+    const bool want = graph_env >= 0 ? (graph_env != 0) : (est_launch_us < 12.0 && pl.path != XINV_PATH_FUSED);
+    if (!want || max_sweeps < 2 * (int64_t)check_every * R.Kf) return XINV_OK;
+    check_every = (check_every + 1) & ~1;
+    if (!ws->gstream) HIPCHK(hipStreamCreateWithFlags(&ws->gstream, hipStreamNonBlocking));
+    hipGraph_t g = nullptr;
+    if (hipStreamBeginCapture(ws->gstream, hipStreamCaptureModeRelaxed) == hipSuccess) {
+        int r = XINV_OK;
+        for (int i = 0; i < check_every && r == XINV_OK; i++)
+            r = launch_planned(p, pl, ws, ws->gstream, R.Kf, R.buf[i & 1], R.buf[(i & 1) ^ 1], 0, p.nbatch, 0, 0);
+        const hipError_t ce = hipStreamEndCapture(ws->gstream, &g);
+        if (!(r == XINV_OK && ce == hipSuccess && g && hipGraphInstantiate(&R.graph_exec, g, nullptr, nullptr, 0) == hipSuccess))
+            R.graph_exec = nullptr;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    (void)hipGetLastError();
+    return XINV_OK;
+}
+
+#if XINV_TEST_HOOKS
+// TEST-HOOKS BUILD ONLY (build/libxinv_hooks.so; the shipped library reads neither switch):
+// XINV_EXP_WATCHDOG="i[,m]" leaves member m (default 0), before launch i, in the state a reducer that timed out leaves
+// behind; XINV_HOOK_SKIP_PUBLISH="i,tile[,m]" makes that tile of launch i withhold its norm partial, so that the
+// reducer of launch i -- the launch's last workgroup, or with the lagged norm the extra workgroup of launch i+1 /
+// k_norm_reduce_lag -- REALLY runs into its (30 ms) watchdog while the later launches are queued behind it.
+static int arm_test_hooks(const Problem &p, Workspace *ws, hipStream_t st, int64_t &wd_at, int64_t &wd_member)
+{
+    if (const char *e = getenv("XINV_EXP_WATCHDOG")) {
+        wd_at = atoll(e);
+        if (const char *c = strchr(e, ',')) wd_member = atoll(c + 1);
+        if (wd_member < 0 || wd_member >= p.nbatch) wd_at = -1;
+    }
+    t_hook_record = nullptr;
+    if (const char *e = getenv("XINV_HOOK_SKIP_PUBLISH")) {
+        long long li = -1, tile = -1, mem = 0;
+        if (sscanf(e, "%lld,%lld,%lld", &li, &tile, &mem) >= 2 && li >= 0 && tile >= 0 && mem >= 0 && mem < p.nbatch) {
+            if (!ws->d_hook) HIPCHK(hipMalloc((void **)&ws->d_hook, 3 * sizeof(int)));
+            const int rec[3] = {(int)tile, (int)(li + 1), (int)mem};      // (launch i publishes with tag i + 1)
+            HIPCHK(hipMemcpyAsync(ws->d_hook, rec, sizeof rec, hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+            t_hook_record = ws->d_hook;
+        }
+    }
+    return XINV_OK;
+}
+#endif
+
+// Watchdog recovery of member m.  A member whose in-kernel norm reduction gave up waiting for a partial (watchdog,
+// overflow == 2; never seen in a run so far) is finished here instead of failing the call: the reducer stops the member
+// BEFORE applying the stop rule to any sweep of its launch, so the control block still describes the state at the start
+// of that launch and the launch's source buffer is intact (every later launch was a no-op for the member).  From there:
+// one sweep per launch without in-kernel norm, ping-pong between that source and the launch's own output (the two-buffer
+// redo of xinv_rotation.h), then the two separate norm kernels of the colour path (k_norm_partial / k_norm_final: no
+// waiting on other workgroups) -- the same sweeps and the same stop rule; the partial sums are added in another order
+// than the tiles' (flags[1] agrees to rounding).
+static int recover_member(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, SweepRun &R, int64_t m)
+{
+    const int64_t n = p.zc * p.yc * p.xc, max_sweeps = p.stop.mxLoop + 1;
+    if (pl.path != XINV_PATH_FUSED) { t_err = "internal: watchdog flag outside the fused path"; return XINV_ERR_HIP; }
+    HIPCHK(hipStreamSynchronize(st));                    // (queued no-op launches)
+    XinvCtl *hcm = const_cast<XinvCtl *>(R.hc) + m;
+    const int64_t L = hcm->loop;
+    const int64_t i = xinv_launch_of(R.bound.data(), (int64_t)R.dstb.size(), L + 1);
+    if (i < 0 || R.bound[(size_t)i] != L) {
+        t_err = "internal: norm partials of a sweep launch never arrived (watchdog) and the control block is not at a launch boundary";
+        return XINV_ERR_HIP;
+    }
+    int rc;
+    if ((rc = ensure_dev(&ws->wd_part, &ws->wd_part_cap, (size_t)XINV_NORM_BLOCKS * (sizeof(double) + sizeof(long long))))) return rc;
+    hipLaunchKernelGGL(k_ctl_resume, dim3(1), dim3(1), 0, st, ws->ctl + m);
+    NormArgs na;
+    memset(&na, 0, sizeof na);
+    na.sS = p.sS; na.n = n; na.undef = p.sc_.undef;
+    na.psum = (double *)ws->wd_part - m * XINV_NORM_BLOCKS;          // (the kernels index by member)
+    na.pcnt = (long long *)((char *)ws->wd_part + XINV_NORM_BLOCKS * sizeof(double)) - m * XINV_NORM_BLOCKS;
+    na.ctl = ws->ctl; na.stop = p.stop; na.force = 0; na.member0 = m;
+    const int nblk = (int)std::min<int64_t>(XINV_NORM_BLOCKS, std::max<int64_t>(1, n / 2048));
+    const XinvRedo r = xinv_redo(R.srcb[(size_t)i], R.dstb[(size_t)i], 2);
+    int64_t s = L;
+    bool fin = false;
+    while (!fin && s < max_sweeps) {
+        const int64_t burst = std::min<int64_t>(32, max_sweeps - s);
+        for (int64_t q = 0; q < burst; q++, s++) {
+            // (biharmonic form, 'extend': the in-place pre-pass of the launch being redone has already run on
+            //  its source -- k_extend_bih precedes the sweep kernel whose reducer timed out -- and the periodic
+            //  one is not idempotent: the first recovery sweep skips it.  The test-hooks switch
+            //  XINV_EXP_WATCHDOG stops the member BEFORE that launch: no hooks case combines it with this form.)
+            const bool prepass = !(s == L && p.kind == KIND_BIH2D && p.BCy == XINV_BC_EXTEND);
+            double *dst = R.buf[xinv_redo_write(r, s - L)];
+            if ((rc = launch_planned(p, pl, ws, st, 1, R.buf[xinv_redo_read(r, s - L)], dst, m, 1, 0, 1, 0, nullptr, nullptr, prepass))) return rc;
+            na.S = dst;
+            hipLaunchKernelGGL(k_norm_partial, dim3(nblk, 1, 1), dim3(256, 1, 1), 0, st, na);
+            hipLaunchKernelGGL(k_norm_final, dim3(1, 1, 1), dim3(64, 1, 1), 0, st, na, nblk);
+        }
+        HIPCHK(hipMemcpyAsync(hcm, ws->ctl + m, sizeof(XinvCtl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        fin = hcm->done != 0;
+    }
+    if (!fin || hcm->overflow == 2) {
+        t_err = "internal: norm partials of a sweep launch never arrived (watchdog) and the recovery did not finish";
+        return XINV_ERR_HIP;
+    }
+    if (R.rec_where.empty()) R.rec_where.assign((size_t)p.nbatch, -1);
+    // sweeps the recovery applied before the stop rule fired (launches after that were no-ops)
+    R.rec_where[(size_t)m] = xinv_redo_result(r, hcm->sweeps - L);
+    t_stats.recovered_members++;
+    return XINV_OK;
+}
+
+// workspace, then chunks of launches with pipelined polling of the device-side stop flags, then the recovery of any
+// member whose norm reduction timed out
+static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt, Workspace *ws, hipStream_t st,
+                      SweepRun &R)
+{
+    const int64_t n = p.zc * p.yc * p.xc;
+    const bool fused = pl.path == XINV_PATH_FUSED;
     const int64_t max_sweeps = p.stop.mxLoop + 1;       // numbas.py:410: loop >= mxLoop stops
-    const int Kf = R.Kf = (pl.path == XINV_PATH_FUSED) ? pl.K : 1;
-    int check_every = opt.check_every;
-    const double sweep_rate = (pl.path != XINV_PATH_FUSED) ? 4.0e4 : (pl.pipe ? 6.0e5 : (is3d(p.kind) ? 2.5e5 : 3.0e5));   // points per us
+    const int Kf = R.Kf = fused ? pl.K : 1;
+    const double sweep_rate = !fused ? 4.0e4 : (pl.pipe ? 6.0e5 : (is3d(p.kind) ? 2.5e5 : 3.0e5));   // points per us
     const double est_pass_us = (double)p.nbatch * (double)n * Kf / sweep_rate;
-    if (check_every <= 0) {
-        // poll the device stop flags about every 2 ms of sweeping (fused kernels run at roughly
-        // 2e5 points per microsecond, the colour path at a quarter of that); launches issued after
-        // a member has stopped are no-ops of a few microseconds each
-        // (round 3: the pipelined 2-D pass runs at 6-7e5 points per microsecond; with the round-1 constant a 500-sweep
-        //  solve at 3600x1800 was polled 18 times -- each poll ends a chunk: one-workgroup norm reduction of the lagged
-        //  launch + control-block copy, ~10 us of idle GPU -- 4 % of the solve)
-        const double est_us = std::max(4.0, est_pass_us);
-        check_every = (int)std::min(256.0, std::max(4.0, 2000.0 / est_us));
-        // (a non-positive tolerance can never stop a solve -- the reference tests' idiom for a fixed number of sweeps,
-        //  tests/test_GeoAdjustment.py:31 -- only an overflow or, in the standard form, a zero norm can: nothing worth a
-        //  poll every 2 ms, each of which holds the next launch back for ~10 us)
-        if (p.stop.tolerance <= 0.0 && pl.path == XINV_PATH_FUSED) check_every = 256;
-    }
-    R.buf[0] = p.S; R.buf[1] = S2; R.buf[2] = nullptr;
+    // (a solve of ONE launch -- the frames of apps.animate_iteration -- has nothing to overlap the reduction with: its own
+    //  last workgroup reduces, one kernel launch less per frame)
+    const bool lag_cand = lag_candidate(p, pl, opt), lag_ok = lag_cand && max_sweeps > (int64_t)Kf;
+    // ---- workspace (the colour path's biharmonic row-class kernel has S2 as its side buffer) ------------------------
+    int rc = solve_workspace(ws, st, p.nbatch, true, partial_bytes(p, pl), lag_cand,
+                             (fused || p.kind == KIND_BIH2D) ? (p.nbatch - 1) * p.sS + n : 0, lag_ok);
+    if (rc) return rc;
+    solve_init(ws, st, p.nbatch, fused ? (lag_cand ? 2 : 1) * ws->partials_half : 0);
+    R.buf[0] = p.S; R.buf[1] = fused ? ws->S2 : nullptr;
+    int check_every = poll_every(p, pl, opt, est_pass_us);
+    if ((rc = capture_chunk(p, pl, opt, ws, R, max_sweeps, check_every))) return rc;
+    const bool use_graph = R.graph_exec != nullptr;
+    const bool lag = R.lag = lag_ok && !use_graph;
+    if (lag) { R.buf[2] = ws->S3; R.nbuf = 3; }
     double **buf = R.buf;
     std::vector<int64_t> &bound = R.bound;
     int64_t &launched = R.launched, &nlaunch = R.nlaunch;
-    double &ms_total = R.ms_total;
-    bool all_done = false;
-    // A chunk = `check_every` launches followed by an asynchronous copy of the control blocks.
-    // Polling is pipelined: chunk c+1 is queued BEFORE the host waits for chunk c's copy, so the
-    // GPU never idles on the host's reaction time; once every member has stopped, the launches
-    // already queued are no-ops (each kernel returns on ctl.done).
-    // one sweep launch (fused: K sweeps from buf[cur] into buf[cur^1]; colour path: one sweep in place)
-#if XINV_EXPERIMENTS
-    static const int exp_noctl = XINV_ENV_INT("XINV_EXP_NOCTL", 0);   // timing experiment (variant builds only): launches without norm / stop rule
-#else
-    constexpr int exp_noctl = 0;
-#endif
-    auto launch_one = [&](hipStream_t s, int cur, int k) -> int {
-        return launch_planned(p, pl, ws, s, k, buf[cur], buf[cur ^ 1], 0, p.nbatch, exp_noctl, exp_noctl);
-    };
-    // Small problems are bound by the host's launch rate (a 151x251 coloured sweep is six launches
-    // of 2-3 us each): a full chunk is captured once into a hipGraph on an engine-owned stream and
-    // replayed into the caller's stream.  The chunk has an even number of launches, so the
-    // ping-pong parity at its start is always 0.
-    bool use_graph = false;
-    {
-        const int graph_env = opt.graph ? (opt.graph > 0 ? 1 : 0) : XINV_ENV_INT("XINV_GRAPH", -1);
-        const double est_launch_us = (double)p.nbatch * (double)n * Kf /
-                                     ((pl.path == XINV_PATH_FUSED) ? 2.0e5 : 4.0e4);
-        // Replay pays on the colour path only (six or more tiny launches per sweep: 25.8 -> 22.2 us per sweep
-        // at 151x251); for the fused kernels it gained nothing (round 1; C1: 2.5 ms replayed against 1.9 ms
-        // per 500 sweeps with plain launches and the lagged norm, which excludes replay).  XINV_GRAPH=1 forces it.
-        const bool want = graph_env >= 0 ? (graph_env != 0) : (est_launch_us < 12.0 && pl.path != XINV_PATH_FUSED);
-        if (want && max_sweeps >= 2 * (int64_t)check_every * Kf) {
-            check_every = (check_every + 1) & ~1;
-            if (!ws->gstream) HIPCHK(hipStreamCreateWithFlags(&ws->gstream, hipStreamNonBlocking));
-            hipGraph_t g = nullptr;
-            if (hipStreamBeginCapture(ws->gstream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                int r = XINV_OK;
-                for (int i = 0; i < check_every && r == XINV_OK; i++) r = launch_one(ws->gstream, i & 1, Kf);
-                const hipError_t ce = hipStreamEndCapture(ws->gstream, &g);
-                if (r == XINV_OK && ce == hipSuccess && g &&
-                    hipGraphInstantiate(&R.graph_exec, g, nullptr, nullptr, 0) == hipSuccess)
-                    use_graph = true;
-                if (g) (void)hipGraphDestroy(g);
-            }
-            (void)hipGetLastError();                       // a failed capture falls back to plain launches
-        }
-    }
-    // (a solve of ONE launch -- the frames of apps.animate_iteration -- has nothing to overlap the reduction with: its own
-    //  last workgroup reduces, one kernel launch less per frame)
-    const bool lag = R.lag = lag_cand && !use_graph && !exp_noctl && max_sweeps > (int64_t)Kf;
-    NormLagArgs lag_pending[XINV_MAX_LANES];               // per lane (one lane: [0])
+    NormLagArgs lag_pending[XINV_MAX_LANES];             // per lane (one lane: [0])
     memset(lag_pending, 0, sizeof lag_pending);
-    if (lag) {
-        const size_t need = (size_t)((p.nbatch - 1) * p.sS + n) * sizeof(double);
-        rc = ensure_dev(&ws->S3, &ws->S3_cap, need);
-        if (rc) return rc;
-        R.buf[2] = ws->S3; R.nbuf = 3;
-    }
     // Masked-tile skipping: the skipped tiles' constant share of the norm, and their copy into every buffer S rotates
     // through (they are never written by the sweep launches).  Nobody needs either before the SECOND launch when the norm
     // is lagged -- launch 0 reads the caller's S and writes the active tiles of S2, its norm is evaluated in launch 1 --
     // so for one slice (one chain) the four small kernels (~40 us) run on a side stream beside launch 0.
     bool side_pending = false;
     struct SideGuard { Workspace *w; bool *pending; ~SideGuard() { if (*pending) (void)hipStreamSynchronize(w->s_side); } } side_guard{ws, &side_pending};
-    if (pl.path == XINV_PATH_FUSED && pl.skip) {
+    if (fused && pl.skip) {
         hipStream_t sk = st;
         if (lag && p.nbatch == 1) {
             if (!ws->s_side) {
@@ -252,7 +375,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
         // (one launch: every skipped tile's share of the norm, its copy into the other buffers, and -- by the block that
         //  arrives last -- the member's sum; k_skip_norm_tile / k_skip_norm_sum / k_copy_skipped until round 4)
         hipLaunchKernelGGL(k_skip_tiles, dim3((unsigned)pl.nskip, (unsigned)p.nbatch, 1), dim3(64), 0, sk,
-                           pl.skipna, S2, lag ? ws->S3 : (double *)nullptr);
+                           pl.skipna, buf[1], lag ? ws->S3 : (double *)nullptr);
         HIPCHK(hipGetLastError());
         if (sk != st) { HIPCHK(hipEventRecord(ws->ev_side1, sk)); side_pending = true; }
     }
@@ -267,7 +390,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
     // for the host on a third stream behind both chains; everything is joined back into the caller's stream below.
     const int lanes_env = opt.lanes > 0 ? opt.lanes : XINV_ENV_INT("XINV_LANES", -1);
     int nlane = 1;
-    if (!use_graph && !exp_noctl && pl.path == XINV_PATH_FUSED)
+    if (!use_graph && fused)
         nlane = (int)std::min<int64_t>(p.nbatch, lanes_env >= 0 ? std::max(1, std::min(lanes_env, XINV_MAX_LANES)) : lane_rule(p, est_pass_us));
     const bool two = nlane > 1;
     R.lanes = nlane;
@@ -281,98 +404,26 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
         Workspace *w; int n; bool poll;
         ~LaneGuard() { for (int l = 1; l < n; l++) (void)hipStreamSynchronize(w->s_lane[l]); if (poll) (void)hipStreamSynchronize(w->s_poll); }
     } lane_guard{ws, nlane, side_poll};
-    if (side_poll) {
-        if (!ws->s_poll) {
-            for (int l = 1; l < XINV_MAX_LANES; l++) HIPCHK(hipStreamCreateWithFlags(&ws->s_lane[l], hipStreamNonBlocking));
-            HIPCHK(hipStreamCreateWithFlags(&ws->s_poll, hipStreamNonBlocking));
-            for (int l = 0; l < XINV_MAX_LANES; l++)
-                for (int q = 0; q < 2; q++) HIPCHK(hipEventCreateWithFlags(&ws->ev_lane[l][q], hipEventDisableTiming));
-            HIPCHK(hipEventCreate(&ws->ev_s));
-        }
+    if (side_poll && !ws->s_poll) {
+        for (int l = 1; l < XINV_MAX_LANES; l++) HIPCHK(hipStreamCreateWithFlags(&ws->s_lane[l], hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&ws->s_poll, hipStreamNonBlocking));
+        for (int l = 0; l < XINV_MAX_LANES; l++)
+            for (int q = 0; q < 2; q++) HIPCHK(hipEventCreateWithFlags(&ws->ev_lane[l][q], hipEventDisableTiming));
+        HIPCHK(hipEventCreate(&ws->ev_s));
     }
     if (two) {
         HIPCHK(hipEventRecord(ws->ev_s, st));            // fork: everything queued so far (workspace set-up) precedes every chain
         for (int l = 1; l < nlane; l++) HIPCHK(hipStreamWaitEvent(ws->s_lane[l], ws->ev_s, 0));
     }
-    // Launch number i of the solve (fused path): k sweeps from buf[srcb[i]] into buf[dstb[i]]; srcb[0] = 0 (the caller's
-    // S), srcb[i] = dstb[i-1].  Two buffers (no lagged norm): ping-pong.  Three (lagged norm): the decision about pass
-    // i-1 arrives while pass i runs, so pass i must leave the source of pass i-1 intact (finalise() redoes a pass the
-    // stop rule fired in from it): dstb[i] is the buffer that is neither srcb[i] nor srcb[i-1] -- a rotation.  Where
-    // the rotation ends decides whether finalise() has to copy the result back into the caller's array (52 MB at
-    // 3600x1800: ~30 us of a 4.3 ms solve).  Evaluating the pending pass BEFORE launch i (flush_lag: one small kernel)
-    // lifts the constraint for that launch -- pass i is then a no-op for a member that stopped in pass i-1 -- and it
-    // may write into srcb[i-1], which REVERSES the rotation: with nl launches to the sweep budget, forward for f and
-    // backward for nl - f ends in buffer (2 f - nl) mod 3, so one reversal at f = nl - 1 (nl mod 3 == 2) or nl - 2
-    // (nl mod 3 == 1) brings an un-converged solve home to buffer 0.  A solve that stops earlier copies, as before.
-    const int64_t nl_budget = (max_sweeps + Kf - 1) / Kf;
-    const int64_t flip_at = (!lag || nl_budget % 3 == 0) ? -1 : (nl_budget % 3 == 2 ? nl_budget - 1 : nl_budget - 2);
+    const int64_t flip_at = xinv_flip_at(lag, (max_sweeps + Kf - 1) / Kf);
+#if XINV_TEST_HOOKS
     int64_t wd_at = -1, wd_member = 0;
-#if XINV_TEST_HOOKS
-    // TEST-HOOKS BUILD ONLY (build/libxinv_hooks.so; the shipped library reads neither switch):
-    // XINV_EXP_WATCHDOG="i[,m]" leaves member m (default 0), before launch i, in the state a reducer that timed out leaves
-    // behind; XINV_HOOK_SKIP_PUBLISH="i,tile[,m]" makes that tile of launch i withhold its norm partial, so that the
-    // reducer of launch i -- the launch's last workgroup, or with the lagged norm the extra workgroup of launch i+1 /
-    // k_norm_reduce_lag -- REALLY runs into its (30 ms) watchdog while the later launches are queued behind it.
-    if (const char *e = getenv("XINV_EXP_WATCHDOG")) {
-        wd_at = atoll(e);
-        if (const char *c = strchr(e, ',')) wd_member = atoll(c + 1);
-        if (wd_member < 0 || wd_member >= p.nbatch) wd_at = -1;
-    }
     struct HookGuard { ~HookGuard() { t_hook_record = nullptr; } } hook_guard;
-    t_hook_record = nullptr;
-    if (const char *e = getenv("XINV_HOOK_SKIP_PUBLISH")) {
-        long long li = -1, tile = -1, mem = 0;
-        if (sscanf(e, "%lld,%lld,%lld", &li, &tile, &mem) >= 2 && li >= 0 && tile >= 0 && mem >= 0 && mem < p.nbatch) {
-            if (!ws->d_hook) HIPCHK(hipMalloc((void **)&ws->d_hook, 3 * sizeof(int)));
-            const int rec[3] = {(int)tile, (int)(li + 1), (int)mem};      // (launch i publishes with tag i + 1)
-            HIPCHK(hipMemcpyAsync(ws->d_hook, rec, sizeof rec, hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-            t_hook_record = ws->d_hook;
-        }
-    }
+    if ((rc = arm_test_hooks(p, ws, st, wd_at, wd_member))) return rc;
 #endif
-    std::function<int()> flush_lag;                      // (defined below; launch_idx flushes before a rotation reversal)
-    auto launch_idx = [&](int64_t i, int k) -> int {
-#if XINV_TEST_HOOKS
-        if (i == wd_at) {                                // (on the stream of the member's lane: ordered before ITS launch i)
-            int l = 0;
-            while (l + 1 < nlane && lane_first(l + 1) <= wd_member) l++;
-            hipLaunchKernelGGL(k_ctl_fake_timeout, dim3(1), dim3(1), 0, l ? ws->s_lane[l] : st, ws->ctl + wd_member);
-        }
-#endif
-        const int sb = (i == 0) ? 0 : R.dstb[(size_t)i - 1];
-        int db;
-        if (R.nbuf == 2) db = sb ^ 1;
-        else if (i == 0) db = 1;
-        else if (i == flip_at) {                         // (the pending pass is evaluated first: its source is free)
-            const int r = flush_lag(); if (r) return r;
-            db = R.srcb[(size_t)i - 1];
-        } else db = 3 - sb - R.srcb[(size_t)i - 1];
-        R.srcb.push_back((signed char)sb); R.dstb.push_back((signed char)db);
-        const double *src = buf[sb];
-        double *dst = buf[db];
-        if (i >= 1) { const int r = side_join(); if (r) return r; }
-        if (exp_noctl == 2)                              // (timing experiment: publish only, nobody reduces)
-            return launch_fused(p, pl, k, src, dst, ws, st, 0, p.nbatch, 1, 0, (unsigned)(i + 1), nullptr);
-        if (!lag && !two) return launch_planned(p, pl, ws, st, k, src, dst, 0, p.nbatch, exp_noctl, exp_noctl);
-        for (int l = 0; l < nlane; l++) {                // (one lane: the whole batch on the caller's stream)
-            hipStream_t sl = l ? ws->s_lane[l] : st;
-            const int64_t m0 = lane_first(l), nm = lane_first(l + 1) - m0;
-            if (!lag) {
-                const int r = launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0);
-                if (r) return r;
-                continue;
-            }
-            NormLagArgs la;
-            const int r = launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0, (unsigned)(i + 1), &la, &lag_pending[l]);
-            if (r) return r;
-            lag_pending[l] = la;                         // evaluated by the lane's next launch, or by flush_lag()
-        }
-        return XINV_OK;
-    };
     // the last launch of a chunk has no successor yet: its norm is evaluated by a one-workgroup kernel
-    // before the control blocks are copied for the host
-    flush_lag = [&]() -> int {
+    // before the control blocks are copied for the host (and before a rotation reversal: xinv_rot_dst)
+    auto flush_lag = [&]() -> int {
         if (!lag) return XINV_OK;
         { const int r = side_join(); if (r) return r; }
         for (int l = 0; l < nlane; l++) {
@@ -387,33 +438,64 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
         }
         return XINV_OK;
     };
+    // launch i's buffers (fused path): its source is the previous launch's destination (the caller's S for launch 0)
+    auto rotate = [&](int64_t i) -> int {
+        const int sb = i ? R.dstb[(size_t)i - 1] : 0;
+        const XinvRot r = xinv_rot_dst(i, sb, i ? R.srcb[(size_t)i - 1] : -1, R.nbuf, flip_at);
+        if (r.flush) { const int e = flush_lag(); if (e) return e; }
+        R.srcb.push_back((signed char)sb); R.dstb.push_back((signed char)r.dst);
+        return XINV_OK;
+    };
+    auto launch_idx = [&](int64_t i, int k) -> int {
+#if XINV_TEST_HOOKS
+        if (i == wd_at) {                                // (on the stream of the member's lane: ordered before ITS launch i)
+            int l = 0;
+            while (l + 1 < nlane && lane_first(l + 1) <= wd_member) l++;
+            hipLaunchKernelGGL(k_ctl_fake_timeout, dim3(1), dim3(1), 0, l ? ws->s_lane[l] : st, ws->ctl + wd_member);
+        }
+#endif
+        { const int r = rotate(i); if (r) return r; }
+        const double *src = buf[R.srcb[(size_t)i]];
+        double *dst = buf[R.dstb[(size_t)i]];
+        if (i >= 1) { const int r = side_join(); if (r) return r; }
+        for (int l = 0; l < nlane; l++) {                // (one lane: the whole batch on the caller's stream)
+            hipStream_t sl = l ? ws->s_lane[l] : st;
+            const int64_t m0 = lane_first(l), nm = lane_first(l + 1) - m0;
+            NormLagArgs la;
+            const int r = lag ? launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0, (unsigned)(i + 1), &la, &lag_pending[l])
+                              : launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0);
+            if (r) return r;
+            if (lag) lag_pending[l] = la;                // evaluated by the lane's next launch, or by flush_lag()
+        }
+        return XINV_OK;
+    };
     int last_slot = 0;
-    const bool per_launch_events = opt.timing == 2 && !two && !use_graph && pl.path == XINV_PATH_FUSED;
+    const bool per_launch_events = opt.timing == 2 && !two && !use_graph && fused;
     // (k_ctl_mail, below: one chain on the caller's stream, the fused path, no timing events, a small batch)
-    const bool mail_ok = !side_poll && !opt.timing && pl.path == XINV_PATH_FUSED && p.nbatch <= 64 &&
+    const bool mail_ok = !side_poll && !opt.timing && fused && p.nbatch <= 64 &&
                          (int64_t)p.nbatch * n <= ((int64_t)1 << 21);
     unsigned mail_val[2] = {0u, 0u};
     if (mail_ok && !ws->hmail) {
         HIPCHK(hipHostMalloc((void **)&ws->hmail, 64, XINV_HOST_COHERENT));
         *ws->hmail = 0u;
     }
+    // A chunk = `check_every` launches followed by an asynchronous copy of the control blocks.
+    // Polling is pipelined: chunk c+1 is queued BEFORE the host waits for chunk c's copy, so the
+    // GPU never idles on the host's reaction time; once every member has stopped, the launches
+    // already queued are no-ops (each kernel returns on ctl.done).
     auto issue_chunk = [&](int slot) -> int {
         if (opt.timing && !two) HIPCHK(hipEventRecord(ws->ev0[slot], st));
-        if (use_graph && max_sweeps - launched >= (int64_t)check_every * Kf &&
-            (pl.path != XINV_PATH_FUSED || (bound.size() & 1) == 0)) {
+        if (use_graph && max_sweeps - launched >= (int64_t)check_every * Kf && (!fused || (bound.size() & 1) == 0)) {
             HIPCHK(hipGraphLaunch(R.graph_exec, st));
-            for (int i = 0; i < check_every; i++) {
-                if (pl.path == XINV_PATH_FUSED) {       // (the captured chunk ping-pongs from buffer 0: launch_one)
+            for (int i = 0; i < check_every; i++, launched += Kf, nlaunch++)
+                if (fused) {                             // (the captured chunk ping-pongs from buffer 0: capture_chunk)
+                    const int r = rotate((int64_t)bound.size()); if (r) return r;
                     bound.push_back(launched);
-                    R.srcb.push_back((signed char)(i & 1)); R.dstb.push_back((signed char)((i & 1) ^ 1));
                 }
-                launched += Kf;
-                nlaunch++;
-            }
         } else
         for (int i = 0; i < check_every && launched < max_sweeps; i++) {
             int r;
-            if (pl.path == XINV_PATH_FUSED) {
+            if (fused) {
                 const int k = (int)std::min<int64_t>(Kf, max_sweeps - launched);   // the tail: one shorter pass
                 const bool tev = per_launch_events && R.lev.size() < XINV_MAX_LAUNCH_EVENTS;
                 if (tev && R.lev.empty()) {
@@ -429,7 +511,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
                 bound.push_back(launched);
                 launched += k;
             } else {
-                r = launch_one(st, 0, 1);
+                r = launch_planned(p, pl, ws, st, 1, buf[0], buf[1], 0, p.nbatch, 0, 0);
                 if (r) return r;
                 launched += 1;
             }
@@ -469,7 +551,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
     };
     const XinvCtl *&hc = R.hc;
     hc = ws->hctl;
-    bool more_at_break = false;
+    bool all_done = false, more_at_break = false;
     rc = issue_chunk(0);
     if (rc) return rc;
     for (int c = 0;; c++) {
@@ -491,7 +573,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
         if (opt.timing) {
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, two ? ws->ev_s : ws->ev0[slot], ws->ev1[slot]));
-            if (two) ms_total = ms; else ms_total += ms; // (two lanes: chunks overlap -- from the fork to the end of this chunk)
+            if (two) R.ms_total = ms; else R.ms_total += ms;   // (two lanes: chunks overlap -- from the fork to the end of this chunk)
         }
         hc = ws->hctl + (size_t)slot * p.nbatch;
         all_done = true;
@@ -510,76 +592,11 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
         all_done = true;
         for (int64_t m = 0; m < p.nbatch; m++) all_done = all_done && hc[m].done;
     }
-    if (pl.path != XINV_PATH_FUSED)                      // drain the queued no-op tail (the fused path syncs below)
-        HIPCHK(hipStreamSynchronize(st));
-    if (!all_done && exp_noctl) {                        // (experiment: no norm, no stop rule -- report the timing only)
-        HIPCHK(hipStreamSynchronize(st));
-        t_stats.sweep_launches = nlaunch; t_stats.sweep_ms = ms_total; t_stats.sweeps_per_launch = Kf;
-        t_err = "XINV_EXP_NOCTL: timing experiment, no result";
-        return XINV_ERR_ARG;
-    }
+    if (!fused) HIPCHK(hipStreamSynchronize(st));        // drain the queued no-op tail (the fused path syncs below)
     if (!all_done) { t_err = "internal: sweep budget exhausted before the stop rule fired"; return XINV_ERR_HIP; }
-    // A member whose in-kernel norm reduction gave up waiting for a partial (watchdog, overflow == 2; never seen in
-    // a run so far) is finished here instead of failing the call: the reducer stops the member BEFORE applying the
-    // stop rule to any sweep of its launch, so the control block still describes the state at the start of that
-    // launch and the launch's source buffer is intact (every later launch was a no-op for the member).  From there:
-    // one sweep per launch without in-kernel norm, then the two separate norm kernels of the colour path
-    // (k_norm_partial / k_norm_final: no waiting on other workgroups) -- the same sweeps and the same stop rule; the
-    // partial sums are added in another order than the tiles' (flags[1] agrees to rounding).
+    if (fused) bound.push_back(launched);
     for (int64_t m = 0; m < p.nbatch; m++)
-        if (hc[m].overflow == 2) {
-            if (pl.path != XINV_PATH_FUSED) { t_err = "internal: watchdog flag outside the fused path"; return XINV_ERR_HIP; }
-            HIPCHK(hipStreamSynchronize(st));            // (queued no-op launches)
-            XinvCtl *hcm = const_cast<XinvCtl *>(hc) + m;
-            const int64_t L = hcm->loop;
-            const size_t i = std::lower_bound(bound.begin(), bound.end(), L) - bound.begin();
-            if (i >= bound.size() || bound[i] != L) {
-                t_err = "internal: norm partials of a sweep launch never arrived (watchdog) and the control block is not at a launch boundary";
-                return XINV_ERR_HIP;
-            }
-            rc = ensure_dev(&ws->wd_part, &ws->wd_part_cap, (size_t)XINV_NORM_BLOCKS * (sizeof(double) + sizeof(long long)));
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_ctl_resume, dim3(1), dim3(1), 0, st, ws->ctl + m);
-            NormArgs na;
-            memset(&na, 0, sizeof na);
-            na.sS = p.sS; na.n = n; na.undef = p.sc_.undef;
-            na.psum = (double *)ws->wd_part - m * XINV_NORM_BLOCKS;          // (the kernels index by member)
-            na.pcnt = (long long *)((char *)ws->wd_part + XINV_NORM_BLOCKS * sizeof(double)) - m * XINV_NORM_BLOCKS;
-            na.ctl = ws->ctl; na.stop = p.stop; na.force = 0; na.member0 = m;
-            const int nblk = (int)std::min<int64_t>(XINV_NORM_BLOCKS, std::max<int64_t>(1, n / 2048));
-            const int b0 = R.srcb[i], b1 = R.dstb[i];
-            int a = b0, b = b1;
-            int64_t s = L;
-            bool fin = false;
-            while (!fin && s < max_sweeps) {
-                const int64_t burst = std::min<int64_t>(32, max_sweeps - s);
-                for (int64_t q = 0; q < burst; q++, s++) {
-                    // (biharmonic form, 'extend': the in-place pre-pass of the launch being redone has already run on
-                    //  its source -- k_extend_bih precedes the sweep kernel whose reducer timed out -- and the periodic
-                    //  one is not idempotent: the first recovery sweep skips it.  The test-hooks switch
-                    //  XINV_EXP_WATCHDOG stops the member BEFORE that launch: no hooks case combines it with this form.)
-                    const bool prepass = !(s == L && p.kind == KIND_BIH2D && p.BCy == XINV_BC_EXTEND);
-                    rc = launch_planned(p, pl, ws, st, 1, buf[a], buf[b], m, 1, 0, 1, 0, nullptr, nullptr, prepass);
-                    if (rc) return rc;
-                    na.S = buf[b];
-                    hipLaunchKernelGGL(k_norm_partial, dim3(nblk, 1, 1), dim3(256, 1, 1), 0, st, na);
-                    hipLaunchKernelGGL(k_norm_final, dim3(1, 1, 1), dim3(64, 1, 1), 0, st, na, nblk);
-                    std::swap(a, b);
-                }
-                HIPCHK(hipMemcpyAsync(hcm, ws->ctl + m, sizeof(XinvCtl), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                fin = hcm->done != 0;
-            }
-            if (!fin || hcm->overflow == 2) {
-                t_err = "internal: norm partials of a sweep launch never arrived (watchdog) and the recovery did not finish";
-                return XINV_ERR_HIP;
-            }
-            if (R.rec_where.empty()) R.rec_where.assign((size_t)p.nbatch, -1);
-            // sweeps the recovery applied before the stop rule fired (launches after that were no-ops): parity = buffer
-            R.rec_where[(size_t)m] = ((hcm->sweeps - L) & 1) ? b1 : b0;
-            t_stats.recovered_members++;
-        }
-
+        if (hc[m].overflow == 2 && (rc = recover_member(p, pl, ws, st, R, m))) return rc;
     return XINV_OK;
 }
 
@@ -588,48 +605,24 @@ static int finalise(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t
                     bool stream_ordered = false)
 {
     const int64_t n = p.zc * p.yc * p.xc;
-    int rc = XINV_OK;
-    (void)n; (void)rc;
-    std::vector<int64_t> &bound = R.bound;
+    const std::vector<int64_t> &bound = R.bound;
     double **buf = R.buf;
     const XinvCtl *hc = R.hc;
     int64_t sweeps_max = 0;
     if (pl.path == XINV_PATH_FUSED) {
-        bound.push_back(R.launched);
+        const bool extend_lag = R.lag && p.kind == KIND_BIH2D && p.BCy == XINV_BC_EXTEND;
         for (int64_t m = 0; m < p.nbatch; m++) {
-            if (!R.rec_where.empty() && R.rec_where[(size_t)m] >= 0) {       // finished by the watchdog recovery
-                const int where = R.rec_where[(size_t)m];
-                if (where != 0)
-                    HIPCHK(hipMemcpyAsync(p.S + m * p.sS, buf[where] + m * p.sS, (size_t)n * sizeof(double),
-                                          hipMemcpyDeviceToDevice, st));
-                continue;
-            }
-            const int64_t sw = hc[m].sweeps;
-            // launch i covers sweeps (bound[i], bound[i+1]]; find the one holding sweep `sw`
-            size_t i = std::upper_bound(bound.begin(), bound.end(), sw - 1) - bound.begin() - 1;
-            const int nbuf = R.nbuf;
-            if (i >= R.dstb.size()) { t_err = "internal: final sweep outside the launches issued"; return XINV_ERR_HIP; }
             int where;                                   // buffer index holding the final state
-            // The biharmonic kernel's 'extend' pre-pass (k_extend_bih) works IN PLACE on the source buffer of its launch.
-            // With the lagged norm the decision about pass i arrives while pass i+1 runs: that pass's pre-pass has then
-            // already copied interior rows into the boundary rows of pass i's OUTPUT -- the final state -- which the
-            // reference leaves as sweep i's own pre-pass made them (found by the extended fuzz at the end of round 4:
-            // rows 0, 1, yc-2, yc-1 of a tolerance stop).  Pass i is redone from its source, which nothing has touched
-            // but pass i's own pre-pass -- not applied again: the periodic one (r0 <- r1, then r1 <- r2) is not idempotent.
-            const bool prepass_hit = R.lag && p.kind == KIND_BIH2D && p.BCy == XINV_BC_EXTEND && i + 2 < bound.size();
-            if (bound[i + 1] == sw && !prepass_hit) {
-                where = R.dstb[i];
-            } else {                                     // stopped inside a K-sweep launch: redo from its source
-                const int src0 = R.srcb[i];
-                int cur = src0;                          // (intact: with the lagged norm the passes after i+1 did nothing)
-                int nxt = R.dstb[i];                     // the pass's own output: free to overwrite
-                const int spare = (nbuf == 3) ? 3 - cur - nxt : cur;
-                for (int64_t s = bound[i]; s < sw; s++) {
-                    rc = launch_planned(p, pl, ws, st, 1, buf[cur], buf[nxt], m, 1, 1, 1, 0, nullptr, nullptr, !prepass_hit);
-                    if (rc) return rc;
-                    const int t = cur; cur = nxt; nxt = (nbuf == 3 && t == src0) ? spare : t;
+            if (!R.rec_where.empty() && R.rec_where[(size_t)m] >= 0) where = R.rec_where[(size_t)m];   // (the watchdog recovery's)
+            else {
+                const XinvWhere w = xinv_where(bound.data(), (int64_t)R.dstb.size(), R.srcb.data(), R.dstb.data(), R.nbuf,
+                                               extend_lag, hc[m].sweeps);
+                if (w.launch < 0) { t_err = "internal: final sweep outside the launches issued"; return XINV_ERR_HIP; }
+                for (int64_t q = 0; q < w.f.redo; q++) {     // stopped inside a K-sweep launch: redo from its source
+                    if (int rc = launch_planned(p, pl, ws, st, 1, buf[xinv_redo_read(w.f.r, q)], buf[xinv_redo_write(w.f.r, q)],
+                                                m, 1, 1, 1, 0, nullptr, nullptr, !w.hit)) return rc;
                 }
-                where = cur;
+                where = w.f.where;
             }
             if (where != 0)
                 HIPCHK(hipMemcpyAsync(p.S + m * p.sS, buf[where] + m * p.sS, (size_t)n * sizeof(double),
@@ -657,28 +650,10 @@ static int finalise(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t
         }
     }
     for (int64_t m = 0; m < p.nbatch; m++) {
-        const XinvCtl &c = hc[m];
-        if (c.overflow) flags[3 * m + 0] = 1.0;
-        if (c.wrote) { flags[3 * m + 1] = c.flag1; flags[3 * m + 2] = c.flag2; }
-        sweeps_max = std::max<int64_t>(sweeps_max, c.sweeps);
+        member_flags(hc[m], flags + 3 * m);
+        sweeps_max = std::max<int64_t>(sweeps_max, hc[m].sweeps);
     }
-    t_stats.path = pl.path;
-    t_stats.colours = pl.ncol;
-    t_stats.sweeps_per_launch = R.Kf;
-    t_stats.rows_per_tile = pl.RY;
-    t_stats.xuniform_mask = (pl.path == XINV_PATH_FUSED || p.kind == KIND_BIH2D) ? (int32_t)pl.um : 0;
-    t_stats.masked_tile_pct = (pl.path == XINV_PATH_FUSED && pl.skip) ? pl.skip_pct : 0;
-    t_stats.masked_tile_ppm = (pl.path == XINV_PATH_FUSED && pl.skip) ? pl.skip_ppm : 0;
-    t_stats.pipelined = (pl.path == XINV_PATH_FUSED && pl.pipe) ? pl.npair : 0;
-    t_stats.lanes = R.lanes;
-    t_stats.point_factor = (pl.path == XINV_PATH_FUSED && pl.pq) ? (pl.alias_ac ? 2 : 1) : 0;
-    if (pl.path == XINV_PATH_FUSED && p.kind == KIND_BIH2D) t_stats.point_factor = pl.bih_vm;
-    if (pl.path == XINV_PATH_FUSED && p.kind == KIND_STD3D && pl.K2) {
-        const int64_t nm = (p.nbatch * 1 / R.lanes) - (p.nbatch * 0 / R.lanes);      // (members of the first lane's launches)
-        const int64_t tiles = (int64_t)pl.nsg2 * pl.nrb2 * nm;
-        t_stats.k_chunks = std::max(1, pl.nkc2);
-        t_stats.cut_tiles = (int32_t)(tiles - p3_whole_tiles(tiles, std::max(1, pl.nkc2), pl.KC2, p.zc, pl.cus));
-    }
+    plan_stats(p, pl, R.lanes, p.nbatch / R.lanes);      // (members of the first lane's launches)
     t_stats.sweep_launches = R.nlaunch;
     t_stats.sweeps_max = sweeps_max;
     t_stats.sweep_ms = R.ms_total;
@@ -972,7 +947,7 @@ static int plan_solve_frames(xinv_plan *h, double *S, double *frames, int64_t nf
     DeviceGuard dg;
     HIPCHK(dg.select(h->device));
     Workspace *ws = get_ws(h->device);
-    std::unique_lock<std::recursive_mutex> lock(ws->busy);
+    std::lock_guard<std::recursive_mutex> lock(ws->busy);  // (held through the restore of S and the ordinary road: recursive)
     rc = ws_ready(ws);
     if (rc) return rc;
     memset(&t_stats, 0, sizeof t_stats);
@@ -986,16 +961,10 @@ static int plan_solve_frames(xinv_plan *h, double *S, double *frames, int64_t nf
         BufSwap sw(ws, &h->bufs);
         Plan pl = pl0;
         pl.skipna.S = S;
-        rc = tail_wait(ws, st);
-        if (rc) return rc;
-        // control blocks of EVERY frame (the workspace's block is theirs for the duration), partials, the twin of S
-        if ((rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)(nframes * nb) * sizeof(XinvCtl)))) return rc;
+        // control blocks of EVERY frame (the workspace's block is theirs for the duration), partials, the twin of S and
+        // S3 for the state before frame 0
+        if ((rc = solve_workspace(ws, st, nframes * nb, false, partial_bytes(p, pl), false, span, true))) return rc;
         ctl_all = ws->ctl;
-        const size_t pbytes = (partial_bytes(p, pl) + 255) & ~(size_t)255;
-        ws->partials_half = pbytes;
-        if ((rc = ensure_dev(&ws->partials, &ws->partials_cap, pbytes))) return rc;
-        if ((rc = ensure_dev(&ws->S2, &ws->S2_cap, (size_t)span * sizeof(double)))) return rc;
-        if ((rc = ensure_dev(&ws->S3, &ws->S3_cap, (size_t)span * sizeof(double)))) return rc;
         HIPCHK(hipMemcpyAsync(ws->S3, S, (size_t)span * sizeof(double), hipMemcpyDeviceToDevice, st));   // (the state before frame 0)
         struct CtlRestore { Workspace *w; XinvCtl *base; ~CtlRestore() { w->ctl = base; } } restore{ws, ctl_all};
         if (pl.skip) {                                   // the skipped tiles' share of the norm and their copy into the twin: once
@@ -1008,8 +977,7 @@ static int plan_solve_frames(xinv_plan *h, double *S, double *frames, int64_t nf
         int64_t nlaunch = 0;
         for (int64_t f = 0; f < nframes; f++) {
             ws->ctl = ctl_all + f * nb;                  // (the launchers take the control blocks from the workspace)
-            hipLaunchKernelGGL(k_solve_init, dim3((unsigned)std::max<int64_t>(cdiv(nb, 256), std::min<int64_t>(256, cdiv((int64_t)(pbytes / 16), 256)))),
-                               dim3(256), 0, st, ws->ctl, nb, (uint4 *)ws->partials, (int64_t)(pbytes / 16));
+            solve_init(ws, st, nb, ws->partials_half);
             for (int64_t i = 0; i < L; i++) {
                 const int k = (int)std::min<int64_t>(Kf, max_sweeps - i * Kf);
                 rc = launch_planned(p, pl, ws, st, k, buf[cur], buf[cur ^ 1], 0, nb, 0, 0);
@@ -1033,19 +1001,16 @@ static int plan_solve_frames(xinv_plan *h, double *S, double *frames, int64_t nf
             for (int64_t m = 0; m < nb; m++) {
                 const XinvCtl &c = hc[(size_t)(f * nb + m)];
                 double *fl = flags + 3 * (nb * f + m);
-                fl[0] = c.overflow ? 1.0 : 0.0; fl[1] = 1.0; fl[2] = 0.0;
-                if (c.wrote) { fl[1] = c.flag1; fl[2] = c.flag2; }
+                fl[0] = 0.0; fl[1] = 1.0; fl[2] = 0.0;
+                member_flags(c, fl);
             }
-        t_stats.path = pl.path; t_stats.colours = pl.ncol; t_stats.sweeps_per_launch = Kf; t_stats.rows_per_tile = pl.RY;
-        t_stats.xuniform_mask = (int32_t)pl.um; t_stats.lanes = 1; t_stats.sweep_launches = nlaunch; t_stats.planned = 1;
-        t_stats.sweeps_max = max_sweeps; t_stats.pipelined = pl.pipe ? pl.npair : 0;
-        t_stats.masked_tile_pct = pl.skip ? pl.skip_pct : 0; t_stats.masked_tile_ppm = pl.skip ? pl.skip_ppm : 0;
+        plan_stats(p, pl, 1, nb);                        // (one chain, every launch covers the whole batch)
+        t_stats.sweep_launches = nlaunch; t_stats.planned = 1; t_stats.sweeps_max = max_sweeps;
         h->solves += good;
         if (bad >= 0)                                    // the state before the first frame that stopped early, back into S
             HIPCHK(hipMemcpyAsync(S, bad > 0 ? frames + (bad - 1) * frame_stride : ws->S3, (size_t)span * sizeof(double),
                                   hipMemcpyDeviceToDevice, st));
     }
     if (bad < 0) return XINV_OK;
-    lock.unlock();
     return slow_from(bad);
 }
