@@ -49,6 +49,7 @@ extern "C" {
 #define XINV_PATH_FUSED  2   /* streaming kernels: a whole sweep (or two) per pass, ping-pong buffers */
 /* (3 was XINV_PATH_SMALL, a register-resident solver for small slices: removed in version 400, it
    never beat the streaming kernels on the shapes it was built for -- DESIGN.md 4.7) */
+#define XINV_PATH_WAVE1D 4   /* stats only: the 1-D form's register-resident kernel (k_std1d), whatever path was asked */
 
 #define XINV_FLAG_NO_XUNIFORM 1  /* stream every coefficient array in full: do not look for rows
                                     that are constant along x                                    */
@@ -372,6 +373,31 @@ int xinv_standard_2d_test_f64_dev(double *S, const double *A, const double *B, c
                                   double ratioQtr, double ratioSqr, double optArg, double undef,
                                   double *flags, int64_t mxLoop, double tolerance,
                                   const xinv_options *opt, void *stream);
+
+/* ---- standard 1-D form (GeoAdjustment, RefStateSWM) ----------------------------------------------------------
+ * xinv_standard_1d_f64 replaces numbas.invert_standard_1D (numbas.py:633-742) called at core.py:272-279:
+ * d/dx(A dS/dx) + B S = F over xc points; strides[]: S, A, B, F (0 = shared).  One member per wavefront (one workgroup of
+ * up to 16 wavefronts above 512 points), the whole solve register-resident in the kernel k_std1d (xinv_std1d.h): red-black
+ * on i & 1 (periodic odd xc: point xc-1 its own colour, run right after colour 0), 'extend' copies S[0] = S[1] and
+ * S[xc-1] = S[xc-2] before every sweep, norm == 0 stops.  The norm of every sweep is summed in a fixed order that depends
+ * on xc alone, so flags[1] and the loop count are the same bits for any batch, budget or device.
+ * Options: sweeps_per_launch = the per-launch sweep budget (0 = 2048; the result does not depend on it), check_every =
+ * launches between two polls of the control blocks (0 = 4); timing = 1 fills sweep_ms.
+ * XINV_ERR_ARG for: xc < 3; xc > 8192 (16 wavefronts x 64 lanes x 8 points); ndev > 1 or -1 (one device only);
+ * f32_mask != 0 (float64 only); prep_flags != 0 (no front-end passes); XINV_FLAG_FMA.  xinv_stats.path = XINV_PATH_WAVE1D. */
+int xinv_standard_1d_f64(double *S, const double *A, const double *B, const double *F, int64_t xc, double delx,
+                         int BCx, double delxSqr, double optArg, double undef, double *flags, int64_t mxLoop,
+                         double tolerance, const xinv_options *opt);
+
+int xinv_standard_1d_f64_batched(double *S, const double *A, const double *B, const double *F, int64_t nbatch,
+                                 const int64_t *strides, int64_t xc, double delx, int BCx, double delxSqr,
+                                 double optArg, double undef, double *flags, int64_t mxLoop, double tolerance,
+                                 const xinv_options *opt);
+
+int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const double *F, int64_t nbatch,
+                             const int64_t *strides, int64_t xc, double delx, int BCx, double delxSqr,
+                             double optArg, double undef, double *flags, int64_t mxLoop, double tolerance,
+                             const xinv_options *opt, void *stream);
 
 /* ---- resident plans: what a solve derives from the coefficient stack, built once -------------------------------
  * The reference calls its kernel again and again on ONE coefficient stack: apps.animate_iteration (apps.py:1031-1044:

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get('XINV_SO') or os.path.join(HERE, 'libxinv_hip.so')
 
 BC_CODES = {'fixed': 0, 'extend': 1, 'periodic': 2}
-PATH_AUTO, PATH_COLOUR, PATH_FUSED = 0, 1, 2
+PATH_AUTO, PATH_COLOUR, PATH_FUSED, PATH_WAVE1D = 0, 1, 2, 4
 PREP_MASK_NAN, PREP_MASK_VALUE, PREP_ROWSCALE, PREP_S_ZERO, PREP_DEMASK = 1, 2, 4, 8, 16     # XINV_PREP_*
 MAX_DEVICES = 16                      # XINV_MAX_DEVICES
 
@@ -68,6 +68,7 @@ EXPORTS = [
     'xinv_general_bih_2d_f64', 'xinv_general_bih_2d_f64_batched', 'xinv_general_bih_2d_f64_dev',
     'xinv_standard_2d_test_f64', 'xinv_standard_2d_test_f64_batched', 'xinv_standard_2d_test_f64_dev',
     'xinv_general_3d_f64', 'xinv_general_3d_f64_batched', 'xinv_general_3d_f64_dev',
+    'xinv_standard_1d_f64', 'xinv_standard_1d_f64_batched', 'xinv_standard_1d_f64_dev',
     'xinv_gm_flow_f64_dev',
     'xinv_abs_norm_f64_dev',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
@@ -126,6 +127,11 @@ def load():
     L.xinv_general_3d_f64.argtypes = [_dp] * 9 + gen3d_scal
     L.xinv_general_3d_f64_batched.argtypes = [_dp] * 9 + [_i64, _ip] + gen3d_scal + [_opt]
     L.xinv_general_3d_f64_dev.argtypes = [_vp] * 9 + [_i64, _ip] + gen3d_scal + [_opt, _vp]
+    # 1-D standard form: xc, delx, BCx, delxSqr, optArg, undef, flags, mxLoop, tolerance
+    std1d_scal = [_i64, _f64, _int, _f64, _f64, _f64, _dp, _i64, _f64]
+    L.xinv_standard_1d_f64.argtypes = [_dp] * 4 + std1d_scal + [_opt]
+    L.xinv_standard_1d_f64_batched.argtypes = [_dp] * 4 + [_i64, _ip] + std1d_scal + [_opt]
+    L.xinv_standard_1d_f64_dev.argtypes = [_vp] * 4 + [_i64, _ip] + std1d_scal + [_opt, _vp]
     L.xinv_gm_flow_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _f64, _int, _vp]
     L.xinv_abs_norm_f64_dev.argtypes = [_vp, _i64, _f64, _dp, _vp]
     # resident plans: the *_dev argument lists without S / flags / mxLoop / tolerance, behind the handle's address

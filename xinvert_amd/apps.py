@@ -156,6 +156,22 @@ def invert_geostrophic(lapPhi, dims, coords='lat-lon', icbc=None,
                      ['f0', 'beta', 'Omega', 'g', 'Omega', 'Rearth'], mParams, iParams)
 
 
+def invert_GeoAdjustment(h0, dims, coords='lat', icbc=None,
+                         mParams=default_mParams, iParams=default_iParams):
+    """Geostrophically adjusted free surface h from the initial one h0 (reference apps.py:148-191):
+    d/dy(A dh/dy) + B h = F, one 1-D problem per slice along dims[0] (register-resident HIP kernel k_std1d)."""
+    return _template(_coeffs_GeoAdjustment, core.inv_standard1D, 1, h0, dims, coords,
+                     icbc, ['g', 'Rearth', 'Omega'], mParams, iParams)
+
+
+def invert_RefStateSWM(Q, dims, coords='lat', icbc=None,
+                       mParams=default_mParams, iParams=default_iParams):
+    """Mass correction of a steady shallow-water reference state from PV contours Q (reference apps.py:194-243);
+    mParams M0 and C0 are aligned with Q by dim name."""
+    return _template(_coeffs_RefStateSWM, core.inv_standard1D, 1, Q, dims, coords,
+                     icbc, ['M0', 'C0', 'g', 'Rearth', 'Omega'], mParams, iParams)
+
+
 def _check_N2(mParams):
     """Stratification profile sanity checks shared by the 3-D apps (reference apps.py:817-823,
     877-883): only array-valued N2 is checked, from its second level on."""
@@ -455,7 +471,9 @@ def _template(coef_func, inv_func, dimLen, F, dims, coords='lat-lon', icbc=None,
     iParams.pop('_lazy', None)
 
     # 2. parameters
-    if dimLen == 2:
+    if dimLen == 1:
+        ps = _cal_params1D(maskF[dims[0]], coords, Rearth=mParams['Rearth'], name=dims[0])
+    elif dimLen == 2:
         ps = _cal_params2D(maskF[dims[0]], maskF[dims[1]], coords, Rearth=mParams['Rearth'])
     elif dimLen == 3:
         ps = _cal_params3D(maskF[dims[0]], maskF[dims[1]], maskF[dims[2]], coords,
@@ -803,6 +821,71 @@ def _coeffs_RefState(Q, dims, coords, mParams, iParams, icbc):
     return maskF.like(maskF.values), initS, _cs(maskF, dims, A, B, C)
 
 
+def _coeffs_GeoAdjustment(h0, dims, coords, mParams, iParams, icbc):
+    """reference apps.py:1527-1553.  B divides by the RAW h0; A (and fH) hold NaN at the first point of the half grid,
+    which no update reads ('extend' and 'fixed' never update point 0)."""
+    g, Omega = mParams['g'], mParams['Omega']
+    maskF, initS, zero = _mask_FS(h0, dims, iParams, icbc)
+    c = coords.lower()
+    if c == 'lat':
+        lats = np.deg2rad(np.asarray(maskF[dims[0]], dtype=np.float64))
+        ax = lambda v: along(v, maskF, dims[0])
+        cosG = ax(np.cos(lats))
+        cosH = ax(np.cos(_half_shift(lats)))
+        f = ax(2 * Omega * np.sin(lats))
+        fH = ax(2 * Omega * np.sin(_half_shift(lats)))
+        h0v = np.asarray(h0.values, dtype=np.float64)
+        A = zero + cosH / fH
+        B = zero - f * cosG / g / h0v
+        F = zero - f * cosG / g
+    elif c == 'cartesian':
+        raise Exception('not supported for cartesian coordinates')
+    else:
+        raise Exception('unsupported coords ' + coords + ', should be in [lat, cartesian]')
+    return maskF.like(F), initS, (A, B)
+
+
+def _diff_2nd(M, cosH, delY, axis):
+    """diff_2nd of reference apps.py:1483-1493 along `axis` (zero at both ends)."""
+    M = np.moveaxis(np.asarray(M, dtype=np.float64), axis, -1)
+    re = np.zeros_like(M)
+    re[..., 1:-1] = (((M[..., 2:] - M[..., 1:-1]) / cosH[2:]) -
+                     ((M[..., 1:-1] - M[..., :-2]) / cosH[1:-1])) / (delY ** 2)
+    return np.moveaxis(re, -1, axis)
+
+
+def _coeffs_RefStateSWM(Q, dims, coords, mParams, iParams, icbc):
+    """reference apps.py:1470-1524.  B multiplies by the MASKED forcing; acos < 0 takes -0.1 acos; cosH holds NaN at
+    the first point of the half grid."""
+    M0, C0, g = mParams['M0'], mParams['C0'], mParams['g']
+    Rearth, Omega = mParams['Rearth'], mParams['Omega']
+    maskF, initS, zero = _mask_FS(Q, dims, iParams, icbc)
+    c = coords.lower()
+    if c == 'lat':
+        lats = np.deg2rad(np.asarray(maskF[dims[0]], dtype=np.float64))
+        cosH1 = np.cos(_half_shift(lats))
+        ax = lambda v: along(v, maskF, dims[0])
+        cosH = ax(cosH1)
+        asin = ax(Rearth * np.sin(lats))
+        acos = Rearth * np.cos(lats)
+        acos = ax(np.where(acos < 0, -acos * 0.1, acos))
+        Mv = np.asarray(aligned(M0, maskF), dtype=np.float64)
+        axis = maskF.axis(dims[0])
+        if Mv.ndim != maskF.values.ndim or Mv.shape[axis] != len(lats):
+            raise Exception('mParams[\'M0\'] must vary along %s' % dims[0])
+        diff = _diff_2nd(Mv, cosH1, np.abs(lats[0] - lats[1]) * Rearth, axis)
+        C0a = aligned(C0, maskF)
+        A = zero + 1.0 / cosH
+        B = zero - C0a * maskF.values * asin / (np.pi * g * acos**3.0)
+        F = zero - (asin * C0a**2.0 / (2.0 * np.pi * g * acos**3.0)) + \
+            (2.0 * np.pi * Omega**2.0 * asin * acos) / g - diff
+    elif c == 'cartesian':
+        raise Exception('not supported for cartesian coordinates')
+    else:
+        raise Exception('unsupported coords ' + coords + ', should be in [z-lat, cartesian]')
+    return maskF.like(np.broadcast_to(F, maskF.shape)), initS, (A, B)
+
+
 def _coeffs_PV2D(PV, dims, coords, mParams, iParams, icbc):
     """reference apps.py:1556-1579 (both coordinate branches are the same expression)."""
     f0, N2 = mParams['f0'], mParams['N2']
@@ -1046,6 +1129,24 @@ def _core_param(p, maskF, dims):
     if p.shape != want:
         raise Exception('field-valued parameter must have the core shape %r' % (want,))
     return p
+
+
+def _cal_params1D(dim1_var, coords, Rearth=default_mParams['Rearth'], name='dim1'):
+    """reference apps.py:2316-2358 (only coords 'lat')."""
+    dim1_var = np.asarray(dim1_var, dtype=np.float64)
+    gc1 = len(dim1_var)
+    del1 = np.diff(dim1_var)[0]
+    _uniform_interval(dim1_var, del1, name)
+    if coords.lower() == 'lat':
+        del1 = np.deg2rad(del1) * Rearth
+    else:
+        raise Exception('unsupported coords for 2D case: ' + coords +
+                        ', should be [lat-lon, cartesian]')
+    del1Sqr = del1 ** 2.0
+    epsilon = np.sin(np.pi/(2.0*gc1+2.0))**2
+    return {'gc1': gc1, 'del1': del1, 'del1Sqr': del1Sqr,
+            'optArg': 2.0 / (1.0 + np.sqrt((2.0 - epsilon) * epsilon)),
+            'flags': np.array([0.0, 1.0, 0.0])}
 
 
 def _cal_params2D(dim2_var, dim1_var, coords, Rearth=default_mParams['Rearth']):

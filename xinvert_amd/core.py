@@ -22,6 +22,14 @@ from .field import Field, LazyForcing, aligned, undef_as
 _undeftmp = -9.99e8
 
 
+def inv_standard1D(A, B, F, S, dims, iParams):
+    """d/dx(A dS/dx) + B S = F along one dim   (reference core.py:234-291; GeoAdjustment, RefStateSWM).
+    Every slice is one member of ONE batched call (single device, float64): the register-resident kernel k_std1d."""
+    if len(dims) != 1:
+        raise Exception('1 dimensions are needed for inversion')
+    return _solve('std1d', (A, B), F, S, dims, iParams)
+
+
 def inv_standard2D(A, B, C, F, S, dims, iParams):
     """d/dy(A dS/dy + B dS/dx) + d/dx(B dS/dy + C dS/dx) = F   (reference core.py:88-155)."""
     if len(dims) != 2:
@@ -371,9 +379,10 @@ def _solve(kind, coefs, F, S, dims, iParams):
     # half the bytes over PCIe -- and is promoted on the device: the same float64 values a host-side promotion gives
     # (xinv_options.f32_mask).  iParams['float32_out']: the solution also comes back as float32, the dtype the
     # reference returns for float32 input (its initS is zeros_like(F)).
-    f32_in = np.asarray(Fsrc).dtype == np.float32 and not iParams.get('no_float32_upload')
+    # (the 1-D form takes float64 only: its arrays are small and promoted here)
+    f32_in = np.asarray(Fsrc).dtype == np.float32 and not iParams.get('no_float32_upload') and kind != 'std1d'
     # (float32 out: only where no float64 first guess would be rounded -- S created here, or handed in as float32)
-    f32_out = bool(iParams.get('float32_out')) and (prep is not None or s_created or np.asarray(S.values).dtype == np.float32)
+    f32_out = kind != 'std1d' and bool(iParams.get('float32_out')) and (prep is not None or s_created or np.asarray(S.values).dtype == np.float32)
     Fv = np.ascontiguousarray(np.transpose(np.asarray(Fsrc, dtype=np.float32 if f32_in else np.float64), perm)
                               ).reshape((nbatch,) + core_shape)
     if prep is not None:
@@ -385,6 +394,12 @@ def _solve(kind, coefs, F, S, dims, iParams):
     for k, c in enumerate(coefs):
         a, st, rc = _prep_coef(c, F, perm, core_shape, nbatch,
                                allow_null=(k == 1 and kind in ('std2d', 'gen2d')))
+        if kind == 'std1d':
+            if a is not None and a.dtype != np.float64:
+                a = a.astype(np.float64)
+            if rc:                                           # (constant along the core dim: the 1-D form takes full members)
+                a = np.ascontiguousarray(np.broadcast_to(a[..., None], a.shape + (core_shape[-1],)))
+                st, rc = (n if st else 0), False
         arrs.append(a)
         strides.append(st)
         rowconst |= (1 << k) if rc else 0
@@ -403,14 +418,18 @@ def _solve(kind, coefs, F, S, dims, iParams):
                        check_every=int(iParams.get('check_every', 0)), rowconst_mask=rowconst,
                        host_chunk=int(iParams.get('host_chunk', 0)),
                        host_inflight=int(iParams.get('host_inflight', 0)),     # (chunk solves in flight; -1: the rolling batch of the 3-D form for any batch)
-                       devices=_device_list(iParams, nbatch, sum(a.nbytes for a, st_ in zip(arrs, strides) if a is not None and st_)),
+                       devices=None if kind == 'std1d' else _device_list(iParams, nbatch, sum(a.nbytes for a, st_ in zip(arrs, strides) if a is not None and st_)),
                        prep=prep,
                        f32_mask=f32_mask,                                        # bit 0: S; bit q + 1: coefficient q (the forcing last)
                        fma=1 if iParams.get('contracted') else 0)      # opt-in XINV_FLAG_FMA (include/xinv.h): NOT the reference's arithmetic
     st = _lib.strides_arg(strides)
     ptrs = [_lib.hptr(a, f32=bool((f32_mask >> k) & 1)) for k, a in enumerate(arrs)]
     mx, tol = int(iParams['mxLoop']), float(iParams['tolerance'])
-    if kind == 'std2d':
+    if kind == 'std1d':                                      # (one device: _device_list is not asked)
+        rc = L.xinv_standard_1d_f64_batched(
+            *ptrs, nbatch, st, iParams['gc1'], float(iParams['del1']), BCs[0], float(iParams['del1Sqr']),
+            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
+    elif kind == 'std2d':
         rc = L.xinv_standard_2d_f64_batched(
             *ptrs, nbatch, st, iParams['gc2'], iParams['gc1'],
             float(iParams['del2']), float(iParams['del1']), BCs[0], BCs[1],

@@ -38,7 +38,7 @@
 #define XINV_AUX_KERNELS            /* the detection / skip-norm helper kernels live in this unit */
 #include "xinv_dispatch.h"          /* argument structs + launchers of the sweep kernels (xinv_tu_*.hip) */
 
-#define XINV_VERSION 600
+#define XINV_VERSION 700
 #define XINV_MEMBER_CHUNK 32768     /* members per launch: grid.y / grid.z are limited to 65535 */
 
 // The shipped library reads NO environment variable: the planner's choices are overridden through xinv_options
@@ -69,6 +69,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_plan.h"        /* planner */
 #include "xinv_sweep.h"       /* sweep loop, finalise, device-pointer solve, resident plans */
 #include "xinv_hostptr.h"     /* host-pointer pipeline, in-call multi-GPU split */
+#include "xinv_std1d_host.h"   /* 1-D standard form: register-resident solve (k_std1d) */
 
 // ------------------------------------------------------------------ problem builders
 static void set_scal2d(Problem &p, double delx, double delxSqr, double ratio, double ratioQtr,
@@ -505,6 +506,51 @@ int xinv_standard_2d_test_f64_dev(double *S, const double *A, const double *B, c
     Problem p = mk_std2dt(S, co, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr,
                           ratioSqr, optArg, undef, mxLoop, tolerance);
     GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+}
+
+// ---- standard 1-D form (k_std1d) --------------------------------------------------------------------------------
+static Std1dProblem mk_std1d(double *S, const double *A, const double *B, const double *F, int64_t nbatch,
+                             const int64_t *st, int64_t xc, int BCx, double delxSqr, double optArg, double undef,
+                             int64_t mxLoop, double tol)
+{
+    Std1dProblem p;
+    memset(&p, 0, sizeof p);
+    p.S = S; p.A = A; p.B = B; p.F = F; p.nbatch = nbatch; p.xc = xc;
+    p.sS = st ? st[0] : xc; p.sA = st ? st[1] : xc; p.sB = st ? st[2] : xc; p.sF = st ? st[3] : xc;
+    p.BCx = BCx; p.delxSqr = delxSqr; p.optArg = optArg; p.undef = undef;
+    p.mxLoop = mxLoop; p.tolerance = tol;
+    return p;
+}
+
+int xinv_standard_1d_f64(double *S, const double *A, const double *B, const double *F, int64_t xc, double delx,
+                         int BCx, double delxSqr, double optArg, double undef, double *flags, int64_t mxLoop,
+                         double tolerance, const xinv_options *opt)
+{
+    (void)delx;
+    Std1dProblem p = mk_std1d(S, A, B, F, 1, nullptr, xc, BCx, delxSqr, optArg, undef, mxLoop, tolerance);
+    GUARD(std1d_solve_host(p, flags, opt))
+}
+
+int xinv_standard_1d_f64_batched(double *S, const double *A, const double *B, const double *F, int64_t nbatch,
+                                 const int64_t *strides, int64_t xc, double delx, int BCx, double delxSqr,
+                                 double optArg, double undef, double *flags, int64_t mxLoop, double tolerance,
+                                 const xinv_options *opt)
+{
+    (void)delx;
+    if (!strides) return fail_arg("null strides");
+    Std1dProblem p = mk_std1d(S, A, B, F, nbatch, strides, xc, BCx, delxSqr, optArg, undef, mxLoop, tolerance);
+    GUARD(std1d_solve_host(p, flags, opt))
+}
+
+int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const double *F, int64_t nbatch,
+                             const int64_t *strides, int64_t xc, double delx, int BCx, double delxSqr,
+                             double optArg, double undef, double *flags, int64_t mxLoop, double tolerance,
+                             const xinv_options *opt, void *stream)
+{
+    (void)delx;
+    if (!strides) return fail_arg("null strides");
+    Std1dProblem p = mk_std1d(S, A, B, F, nbatch, strides, xc, BCx, delxSqr, optArg, undef, mxLoop, tolerance);
+    GUARD(std1d_solve_dev(p, flags, opt, (hipStream_t)stream))
 }
 
 // ---- resident plans (include/xinv.h: "resident plans") ---------------------------------------------------------
