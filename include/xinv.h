@@ -498,6 +498,38 @@ int xinv_gm_flow_f64_dev(const double *S, double *u, double *v, int64_t nbatch, 
  * numbas.absNorm2D/3D, numbas.py:1710-1728 / 1689-1708); *out is a host double. */
 int xinv_abs_norm_f64_dev(const double *S, int64_t n, double undef, double *out, void *stream);
 
+/* ---- finite differences (reference finitediffs.py: FiniteDiff, deriv, deriv2) -----------------------------------------
+ * One launch of k_fd (xinv_fd.h) per call computes up to 4 derivative TERMS of up to 3 inputs at every point and combines
+ * them by `mode`: XINV_FD_EACH 0 (out[t] = term t: deriv, deriv2, grad), XINV_FD_SUM 1 (out[0] = ((0 + term 0) + term 1)
+ * + ...: divg, tension_strain, Laplacian), XINV_FD_DIFF 2 (out[0] = term 0 - term 1: one vorticity component).
+ * Arrays are C-contiguous float64 of shape[ndim] (any dim order; every input and output has that shape; outputs must not
+ * overlap inputs).  Term t is described by iterm[15 t + k] and dterm[6 t + k]:
+ *   iterm  0 kind: 0 centre (numpy.gradient on the BC-padded axis), 1 forward, 2 backward, 3 second difference
+ *          1 input index   2 negate the input (1/0)   3 derivative axis (length >= 2)
+ *          4, 5 BC at the low / high end: 0 fixed, 1 extend, 2 periodic (both ends), 3 reflect
+ *          6 uniform: 1 = the padded coordinate is uniform ((fp - fm) / dterm[2]); 0 = weights at tab[iterm 10]
+ *          7 metric (kind 3): 0 none, 1 add +0.0, 2 add ((-(centre / dterm[4])) * tan[i]) / dterm[5]
+ *          8 pre-weight axis (-1: none): f = input * tab[iterm 12 + index along that axis], before padding
+ *          9 divisor axis (-1: the scalar dterm[3]): the result is divided by tab[iterm 13 + index along that axis]
+ *          10 offset of the centre weights a[n], b[n], c[n] (n = shape[axis]): (a fm + b f0) + c fp
+ *          11 offset of the per-index coordinate differences (forward: c[i] - c[i+1]; backward: c[i-1] - c[i]) or, for
+ *             kind 3, of the squared lower spacings h^2 of the padded coordinate
+ *          12 pre-weight table offset   13 divisor table offset (kind 3: the squared divisor)   14 tan table offset
+ *   dterm  0, 1 fill at the low / high end (fixed BC)   2 2*dx (uniform centre)   3 scalar divisor (kind 3: squared)
+ *          4 the metric's first-derivative divisor   5 the metric's radius
+ * Unused offsets may be -1.  tab[ntab] holds every table (xinv_fd_f64: host array; _dev: device array).  mask_axis >= 0
+ * (mode SUM only): the output is 0 wherever tab[mask_off + index along mask_axis] == 0 (the Laplacian's poles).
+ * Forward / backward write NaN at the far end.  Indexing is 64-bit.  xinv_fd_f64 runs on the current device: it uploads
+ * the inputs and tab, launches once and downloads the outputs; xinv_fd_f64_dev takes device pointers and returns after
+ * queueing the launch on `stream`.  XINV_ERR_ARG (with xinv_last_error) for a bad shape, mode, term count, kind, BC,
+ * mixed periodic BC, axis or table range. */
+int xinv_fd_f64(const double *const *in, int nin, double *const *out, int nout, int ndim, const int64_t *shape,
+                int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
+                int mask_axis, int64_t mask_off);
+int xinv_fd_f64_dev(const double *const *in, int nin, double *const *out, int nout, int ndim, const int64_t *shape,
+                    int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
+                    int mask_axis, int64_t mask_off, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

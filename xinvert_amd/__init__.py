@@ -8,6 +8,8 @@ Layout (only what the hot path needs):
                  (reference xinvert/apps.py)
   dist.py        batch-axis sharding across ranks (one process per GPU) + flags gather
   field.py       minimal labelled array standing in for xarray.DataArray
+  finitediffs.py FiniteDiff / deriv / deriv2 / padBCs: one HIP launch per operator (reference xinvert/finitediffs.py)
+  utils.py       loop_noncore (reference xinvert/utils.py)
 """
 from .field import Field                                           # noqa: F401
 from .core import (inv_standard1D, inv_standard2D, inv_standard2D_test, inv_general2D, inv_general2D_bih,    # noqa: F401
@@ -18,5 +20,7 @@ from .apps import (invert_Poisson, invert_Stommel, invert_StommelMunk, invert_Gi
                    invert_Stommel_test, invert_StommelArons, invert_geostrophic,
                    invert_GeoAdjustment, invert_RefStateSWM,
                    animate_iteration, cal_flow, default_iParams, default_mParams)
+from .utils import loop_noncore                                    # noqa: F401
+from .finitediffs import FiniteDiff, deriv, deriv2, padBCs, DeviceField   # noqa: F401
 
 __version__ = '0.1.0'

@@ -19,6 +19,7 @@ MAX_DEVICES = 16                      # XINV_MAX_DEVICES
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int64)
 _i64, _f64, _int, _vp = ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_void_p
+_pvp = ctypes.POINTER(ctypes.c_void_p)
 
 
 class XinvOptions(ctypes.Structure):
@@ -71,6 +72,7 @@ EXPORTS = [
     'xinv_standard_1d_f64', 'xinv_standard_1d_f64_batched', 'xinv_standard_1d_f64_dev',
     'xinv_gm_flow_f64_dev',
     'xinv_abs_norm_f64_dev',
+    'xinv_fd_f64', 'xinv_fd_f64_dev',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -134,6 +136,10 @@ def load():
     L.xinv_standard_1d_f64_dev.argtypes = [_vp] * 4 + [_i64, _ip] + std1d_scal + [_opt, _vp]
     L.xinv_gm_flow_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _f64, _int, _vp]
     L.xinv_abs_norm_f64_dev.argtypes = [_vp, _i64, _f64, _dp, _vp]
+    # finite differences: in[], nin, out[], nout, ndim, shape, mode, nterms, iterm, dterm, tab, ntab, mask_axis, mask_off
+    fd_args = [_pvp, _int, _pvp, _int, _int, _ip, _int, _int, _ip, _dp, _vp, _i64, _int, _i64]
+    L.xinv_fd_f64.argtypes = fd_args
+    L.xinv_fd_f64_dev.argtypes = fd_args + [_vp]
     # resident plans: the *_dev argument lists without S / flags / mxLoop / tolerance, behind the handle's address
     _pp = ctypes.POINTER(_vp)
     no_tail = lambda scal: scal[:-3]                     # (drop flags, mxLoop, tolerance)

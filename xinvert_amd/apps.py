@@ -394,10 +394,17 @@ def cal_flow(S, dims, coords='lat-lon', BCs=('fixed', 'fixed'), vtype='streamfun
     return to_like(S.like(c1, 'u'), tmpl), to_like(S.like(c2, 'v'), tmpl)
 
 
-def gradient_tables(coord):
+def padded_coord(coord):
+    """The coordinate of a field padded by one point per end, extrapolated linearly (reference finitediffs.py:599-604)."""
+    c = np.asarray(coord, dtype=np.float64)
+    return np.concatenate(([c[0] * 2 - c[1]], c, [c[-1] * 2 - c[-2]]))
+
+
+def gradient_tables(coord, padded=False):
     """What numpy.gradient(f, coord, edge_order=1) (= xarray .differentiate) needs per index:
-    (table[3n+3], uniform) with the non-uniform interior weights a, b, c and {dx, dx_first, dx_last}."""
-    x = np.asarray(coord, dtype=np.float64)
+    (table[3n+3], uniform) with the non-uniform interior weights a, b, c and {dx, dx_first, dx_last}.
+    padded=True: the same for `padded_coord(coord)` (n + 2 points), the axis FiniteDiff's centred derivative runs on."""
+    x = padded_coord(coord) if padded else np.asarray(coord, dtype=np.float64)
     n = x.size
     d = np.diff(x)
     uniform = bool((d == d[0]).all())

@@ -52,6 +52,8 @@ UNITS = [
     ('xinv_tu_bih', 'xinv_tu_bih.hip', ['-mllvm', '-amdgpu-sched-strategy=max-ilp']),
     # the 1-D standard form, register-resident (k_std1d: one member per wavefront or workgroup)
     ('xinv_tu_std1d', 'xinv_tu_std1d.hip', []),
+    # finite differences (FiniteDiff, deriv, deriv2): one streaming launch per call (k_fd)
+    ('xinv_tu_fd', 'xinv_tu_fd.hip', []),
 ]
 # XINV_VARIANT_UNITS="xinv_tu_fused3d,..." (with XINV_BUILD_TAG): only these units are compiled with the extra flags; every
 # other object is taken from the shipped build's build/obj (a variant of one kernel family links in seconds)

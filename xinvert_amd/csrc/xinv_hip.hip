@@ -38,7 +38,7 @@
 #define XINV_AUX_KERNELS            /* the detection / skip-norm helper kernels live in this unit */
 #include "xinv_dispatch.h"          /* argument structs + launchers of the sweep kernels (xinv_tu_*.hip) */
 
-#define XINV_VERSION 700
+#define XINV_VERSION 800
 #define XINV_MEMBER_CHUNK 32768     /* members per launch: grid.y / grid.z are limited to 65535 */
 
 // The shipped library reads NO environment variable: the planner's choices are overridden through xinv_options
@@ -70,6 +70,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_sweep.h"       /* sweep loop, finalise, device-pointer solve, resident plans */
 #include "xinv_hostptr.h"     /* host-pointer pipeline, in-call multi-GPU split */
 #include "xinv_std1d_host.h"   /* 1-D standard form: register-resident solve (k_std1d) */
+#include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
 
 // ------------------------------------------------------------------ problem builders
 static void set_scal2d(Problem &p, double delx, double delxSqr, double ratio, double ratioQtr,
@@ -551,6 +552,34 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
     if (!strides) return fail_arg("null strides");
     Std1dProblem p = mk_std1d(S, A, B, F, nbatch, strides, xc, BCx, delxSqr, optArg, undef, mxLoop, tolerance);
     GUARD(std1d_solve_dev(p, flags, opt, (hipStream_t)stream))
+}
+
+// ---- finite differences (k_fd) ----------------------------------------------------------------------------------
+static FdCall mk_fd(const double *const *in, int nin, double *const *out, int nout, int ndim, const int64_t *shape,
+                    int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
+                    int mask_axis, int64_t mask_off)
+{
+    FdCall c;
+    c.in = in; c.nin = nin; c.out = out; c.nout = nout; c.ndim = ndim; c.shape = shape;
+    c.mode = mode; c.nterms = nterms; c.iterm = iterm; c.dterm = dterm; c.tab = tab; c.ntab = ntab;
+    c.mask_axis = mask_axis; c.mask_off = mask_off;
+    return c;
+}
+
+int xinv_fd_f64(const double *const *in, int nin, double *const *out, int nout, int ndim, const int64_t *shape,
+                int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
+                int mask_axis, int64_t mask_off)
+{
+    GUARD(fd_run_host(mk_fd(in, nin, out, nout, ndim, shape, mode, nterms, iterm, dterm, tab, ntab, mask_axis,
+                            mask_off)))
+}
+
+int xinv_fd_f64_dev(const double *const *in, int nin, double *const *out, int nout, int ndim, const int64_t *shape,
+                    int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
+                    int mask_axis, int64_t mask_off, void *stream)
+{
+    GUARD(fd_run_dev(mk_fd(in, nin, out, nout, ndim, shape, mode, nterms, iterm, dterm, tab, ntab, mask_axis,
+                           mask_off), (hipStream_t)stream))
 }
 
 // ---- resident plans (include/xinv.h: "resident plans") ---------------------------------------------------------
