@@ -530,6 +530,25 @@ int xinv_fd_f64_dev(const double *const *in, int nin, double *const *out, int no
                     int mode, int nterms, const int64_t *iterm, const double *dterm, const double *tab, int64_t ntab,
                     int mask_axis, int64_t mask_off, void *stream);
 
+/* ---- multigrid grid transfers (invert_MultiGrid, xinvert_amd/multigrid.py) ------------------------------------------
+ * Device pointers, [nbatch][core] layout with 1 <= ndim <= 3 core dims (C-contiguous, slowest first); both queue one
+ * launch on `stream` and return.  64-bit indexing.
+ * xinv_mg_restrict_f64_dev: coarse[b][J] = mean of the fine block J_a * ratio[a] + o_a (o_a < ratio[a]; the trailing
+ *   fshape[a] % ratio[a] points belong to no block) over its points that are not `undef` (a NaN undef: the NaN points),
+ *   summed from 0.0 in lexicographic offset order and divided once; `undef` for a block without a valid point.
+ *   coarse has shape fshape[a] / ratio[a]; 1 <= ratio[a] <= fshape[a].
+ * xinv_mg_prolong_f64_dev: fine[b][i] = the d-linear blend of coarse[b] nested from the slowest dim to the fastest,
+ *   ((1 - w) * c[lo] + w * c[hi] per dim), with per-dim tables: idx holds lo[fshape[0]], hi[fshape[0]], lo[fshape[1]],
+ *   ... (every entry in [0, cshape[a])), w holds w[fshape[0]], w[fshape[1]], ...  A fine point is left as it is where
+ *   force (fine forcing, may be NULL) equals `undef`, on index 0 and fshape[a] - 1 of every dim a whose bit is set in
+ *   keep_edges, and where the blend is not finite.  The library cannot check device tables: the caller builds them in
+ *   range (xinvert_amd/multigrid.py). */
+int xinv_mg_restrict_f64_dev(const double *fine, double *coarse, int64_t nbatch, int ndim, const int64_t *fshape,
+                             const int64_t *ratio, double undef, void *stream);
+int xinv_mg_prolong_f64_dev(const double *coarse, double *fine, const double *force, int64_t nbatch, int ndim,
+                            const int64_t *cshape, const int64_t *fshape, const int64_t *idx, const double *w,
+                            int keep_edges, double undef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ Layout (only what the hot path needs):
   field.py       minimal labelled array standing in for xarray.DataArray
   finitediffs.py FiniteDiff / deriv / deriv2 / padBCs: one HIP launch per operator (reference xinvert/finitediffs.py)
   utils.py       loop_noncore (reference xinvert/utils.py)
+  multigrid.py   invert_MultiGrid: coarse-to-fine SOR solves, HIP restriction / prolongation (reference xinvert/apps.py)
 """
 from .field import Field                                           # noqa: F401
 from .core import (inv_standard1D, inv_standard2D, inv_standard2D_test, inv_general2D, inv_general2D_bih,    # noqa: F401
@@ -22,5 +23,6 @@ from .apps import (invert_Poisson, invert_Stommel, invert_StommelMunk, invert_Gi
                    animate_iteration, cal_flow, default_iParams, default_mParams)
 from .utils import loop_noncore                                    # noqa: F401
 from .finitediffs import FiniteDiff, deriv, deriv2, padBCs, DeviceField   # noqa: F401
+from .multigrid import invert_MultiGrid                             # noqa: F401
 
 __version__ = '0.1.0'

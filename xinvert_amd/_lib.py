@@ -73,6 +73,7 @@ EXPORTS = [
     'xinv_gm_flow_f64_dev',
     'xinv_abs_norm_f64_dev',
     'xinv_fd_f64', 'xinv_fd_f64_dev',
+    'xinv_mg_restrict_f64_dev', 'xinv_mg_prolong_f64_dev',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -140,6 +141,10 @@ def load():
     fd_args = [_pvp, _int, _pvp, _int, _int, _ip, _int, _int, _ip, _dp, _vp, _i64, _int, _i64]
     L.xinv_fd_f64.argtypes = fd_args
     L.xinv_fd_f64_dev.argtypes = fd_args + [_vp]
+    # multigrid transfers: restrict(fine, coarse, nbatch, ndim, fshape, ratio, undef, stream);
+    # prolong(coarse, fine, force, nbatch, ndim, cshape, fshape, idx, w, keep_edges, undef, stream)
+    L.xinv_mg_restrict_f64_dev.argtypes = [_vp, _vp, _i64, _int, _ip, _ip, _f64, _vp]
+    L.xinv_mg_prolong_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _int, _ip, _ip, _vp, _vp, _int, _f64, _vp]
     # resident plans: the *_dev argument lists without S / flags / mxLoop / tolerance, behind the handle's address
     _pp = ctypes.POINTER(_vp)
     no_tail = lambda scal: scal[:-3]                     # (drop flags, mxLoop, tolerance)

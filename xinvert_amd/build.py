@@ -54,6 +54,8 @@ UNITS = [
     ('xinv_tu_std1d', 'xinv_tu_std1d.hip', []),
     # finite differences (FiniteDiff, deriv, deriv2): one streaming launch per call (k_fd)
     ('xinv_tu_fd', 'xinv_tu_fd.hip', []),
+    # multigrid grid transfers (invert_MultiGrid): k_mg_restrict, k_mg_prolong
+    ('xinv_tu_mg', 'xinv_tu_mg.hip', []),
 ]
 # XINV_VARIANT_UNITS="xinv_tu_fused3d,..." (with XINV_BUILD_TAG): only these units are compiled with the extra flags; every
 # other object is taken from the shipped build's build/obj (a variant of one kernel family links in seconds)

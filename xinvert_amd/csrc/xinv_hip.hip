@@ -38,7 +38,7 @@
 #define XINV_AUX_KERNELS            /* the detection / skip-norm helper kernels live in this unit */
 #include "xinv_dispatch.h"          /* argument structs + launchers of the sweep kernels (xinv_tu_*.hip) */
 
-#define XINV_VERSION 800
+#define XINV_VERSION 900
 #define XINV_MEMBER_CHUNK 32768     /* members per launch: grid.y / grid.z are limited to 65535 */
 
 // The shipped library reads NO environment variable: the planner's choices are overridden through xinv_options
@@ -71,6 +71,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_hostptr.h"     /* host-pointer pipeline, in-call multi-GPU split */
 #include "xinv_std1d_host.h"   /* 1-D standard form: register-resident solve (k_std1d) */
 #include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
+#include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
 
 // ------------------------------------------------------------------ problem builders
 static void set_scal2d(Problem &p, double delx, double delxSqr, double ratio, double ratioQtr,
@@ -771,6 +772,85 @@ static int abs_norm_dev(const double *S, int64_t n, double undef, double *out, h
 int xinv_abs_norm_f64_dev(const double *S, int64_t n, double undef, double *out, void *stream)
 {
     GUARD(abs_norm_dev(S, n, undef, out, (hipStream_t)stream))
+}
+
+// ---- multigrid grid transfers (k_mg_restrict, k_mg_prolong: xinv_mg.h) -------------------------------------------
+// The core is padded to three dims with leading length-1 dims; blocks of XINV_MG_WG lanes cover one row of the last axis.
+static int mg_shape(int64_t nbatch, int ndim, const int64_t *shape, int64_t n3[3])
+{
+    if (nbatch < 1 || ndim < 1 || ndim > 3 || !shape) return fail_arg("multigrid: need nbatch >= 1 and 1 to 3 core dims");
+    for (int a = 0; a < 3; ++a) n3[a] = a < 3 - ndim ? 1 : shape[a - (3 - ndim)];
+    for (int a = 0; a < 3; ++a)
+        if (n3[a] < 1) return fail_arg("multigrid: a core dim is empty");
+    return XINV_OK;
+}
+
+static int mg_restrict_dev(const double *fine, double *coarse, int64_t nbatch, int ndim, const int64_t *fshape,
+                           const int64_t *ratio, double undef, hipStream_t st)
+{
+    MgRestrictArgs a;
+    memset(&a, 0, sizeof a);
+    if (!fine || !coarse || !ratio) return fail_arg("multigrid restrict: null argument");
+    int rc = mg_shape(nbatch, ndim, fshape, a.fn);
+    if (rc) return rc;
+    for (int a3 = 0; a3 < 3; ++a3) {
+        a.r[a3] = a3 < 3 - ndim ? 1 : ratio[a3 - (3 - ndim)];
+        if (a.r[a3] < 1 || a.fn[a3] / a.r[a3] < 1) return fail_arg("multigrid restrict: need 1 <= ratio <= length");
+        a.cn[a3] = a.fn[a3] / a.r[a3];
+    }
+    a.fine = fine; a.coarse = coarse;
+    a.fslice = a.fn[0] * a.fn[1] * a.fn[2];
+    a.cslice = a.cn[0] * a.cn[1] * a.cn[2];
+    a.rows = nbatch * a.cn[0] * a.cn[1];
+    a.nbx = (a.cn[2] + XINV_MG_WG - 1) / XINV_MG_WG;
+    a.undef = undef; a.nan = undef != undef;
+    xinv_launch_mg_restrict(a, a.rows * a.nbx, st);
+    HIPCHK(hipGetLastError());
+    return XINV_OK;
+}
+
+static int mg_prolong_dev(const double *coarse, double *fine, const double *force, int64_t nbatch, int ndim,
+                          const int64_t *cshape, const int64_t *fshape, const int64_t *idx, const double *w,
+                          int keep_edges, double undef, hipStream_t st)
+{
+    MgProlongArgs a;
+    memset(&a, 0, sizeof a);
+    if (!coarse || !fine || !idx || !w) return fail_arg("multigrid prolong: null argument");
+    int rc = mg_shape(nbatch, ndim, fshape, a.fn);
+    if (!rc) rc = mg_shape(nbatch, ndim, cshape, a.cn);
+    if (rc) return rc;
+    if (keep_edges < 0 || keep_edges >= (1 << ndim)) return fail_arg("multigrid prolong: keep_edges names no core dim");
+    const int pad = 3 - ndim;
+    int64_t off = 0, woff = 0;
+    for (int d = 0; d < ndim; ++d) {               // per core dim: lo[n], hi[n] in idx; w[n] in w
+        const int64_t n = a.fn[pad + d];
+        a.lo[pad + d] = idx + off; a.hi[pad + d] = idx + off + n; a.w[pad + d] = w + woff;
+        off += 2 * n; woff += n;
+        if (keep_edges & (1 << d)) a.keep |= 1 << (pad + d);
+    }
+    a.coarse = coarse; a.fine = fine; a.force = force;
+    a.fslice = a.fn[0] * a.fn[1] * a.fn[2];
+    a.cslice = a.cn[0] * a.cn[1] * a.cn[2];
+    a.rows = nbatch * a.fn[0] * a.fn[1];
+    a.nbx = (a.fn[2] + XINV_MG_WG - 1) / XINV_MG_WG;
+    a.undef = undef; a.nd = ndim;
+    if (xinv_launch_mg_prolong(a, a.rows * a.nbx, st)) return fail_arg("multigrid prolong: no kernel for this rank");
+    HIPCHK(hipGetLastError());
+    return XINV_OK;
+}
+
+int xinv_mg_restrict_f64_dev(const double *fine, double *coarse, int64_t nbatch, int ndim, const int64_t *fshape,
+                             const int64_t *ratio, double undef, void *stream)
+{
+    GUARD(mg_restrict_dev(fine, coarse, nbatch, ndim, fshape, ratio, undef, (hipStream_t)stream))
+}
+
+int xinv_mg_prolong_f64_dev(const double *coarse, double *fine, const double *force, int64_t nbatch, int ndim,
+                            const int64_t *cshape, const int64_t *fshape, const int64_t *idx, const double *w,
+                            int keep_edges, double undef, void *stream)
+{
+    GUARD(mg_prolong_dev(coarse, fine, force, nbatch, ndim, cshape, fshape, idx, w, keep_edges, undef,
+                         (hipStream_t)stream))
 }
 
 } // extern "C"
