@@ -9,7 +9,12 @@ evaluated on the device after every sweep exactly as in production.  Every point
 counted in `value`, masked (land) points included; `value_active` and every roofline fraction count
 only the tiles the kernel actually ran.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--sweeps S] [--dump-outputs DIR] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--sweeps S] [--dump-outputs DIR] [--full] ...
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line
+(N > 1 adds rank 0's stand-alone rerun, n1_value: the N = 1 rate the multi-rank figure is read against).
+--full: also every leg that takes runs of its own (the objects marked [full] below); --no-hbm, --no-parity, --no-configs,
+--no-e2e and --no-cpu leave single legs of a --full run out.
 
 --gpus N > 1 started WITHOUT a torchrun environment launches its own N ranks (torch.distributed.run,
 rendezvous on 127.0.0.1) and fails loudly when fewer than N GPUs are visible; started under torchrun it
@@ -22,7 +27,7 @@ volumes) split over the ranks (strong scaling).
 --inproc: additionally time the other multi-GPU mode: ONE process, host pointers,
 xinv_options.ndev = N (one host thread per GPU inside the call); PCIe-inclusive, reported as `inproc`.
 
-Extra objects in the ONE JSON line rank 0 prints (N = 1, c2):
+Extra objects in the ONE JSON line rank 0 prints (N = 1, c2; [full]: with --full only, null or absent otherwise):
   roofline       the resource that bounds the dominant kernel: the fp64 vector ALU.  achieved = point updates
                  of the tiles that RAN (skipped, fully masked tiles are not counted) x 16 fp64 operations /
                  mean launch duration (HIP events on the solve's stream over the timed region); peak = fp64
@@ -32,17 +37,22 @@ Extra objects in the ONE JSON line rank 0 prints (N = 1, c2):
                  same kernel variant (profiles/traffic.json; counters cannot be read in-process).
                  `hbm_frac` / `hbm_variant` repeat roofline_hbm's figures (the one true HBM fraction of the line) and
                  `configs` a compact copy of the per-configuration table.
-  roofline_hbm   the HBM-bound variant north_star names on a working set far beyond the 256 MiB Infinity
+  roofline_hbm   [full] the HBM-bound variant north_star names on a working set far beyond the 256 MiB Infinity
                  Cache: 8 members with their own A, C, F (2.1 GB), one sweep per pass, every array streamed,
                  every tile run.  `achieved` prices the 40 B per point the variant really streams (S read +
                  write, A, C, F; B is identically zero and never read); `alg48_*` is SURVEY 8(d)'s 48 B figure.
-  configs        one line per other BASELINE configuration (C1, C3 Stommel, C3 Munk, C4, C5) on this GPU at SURVEY
+  configs        [full] one line per other BASELINE configuration (C1, C3 Stommel, C3 Munk, C4, C5) on this GPU at SURVEY
                  8(d)'s sweep counts (500; C5 200) and one GPU's share of the batch (C4 8 of 64, C5 15 of 120):
                  value, kernel, bound, fraction, alg_frac, PMC traffic, and a bitwise parity flag against the oracle.
   rank_values    (N > 1) every rank's own rate on its block; n1_value: rank 0 alone on its block with the others idle
                  (the N = 1 rate for the same per-GPU work); flags_sha256: digest of the gathered per-slice flags.
-  parity         the timed solve repeated from the initial state and compared BIT FOR BIT with the oracle.
-  cpu_baseline   the oracle's lexicographic sweep (the reference's execution model), -march=native build.
+  parity         [full] the timed solve repeated from the initial state and compared BIT FOR BIT with the oracle.
+  sustained, unplanned, mask_sensitivity, contracted, end_to_end
+                 [full] the headline solve for >= 5 s back to back, without a resident plan, with other masks, with the
+                 opt-in contracted arithmetic; host arrays in and out (see the functions that make them).
+  cpu_baseline   [full] the oracle's lexicographic sweep (the reference's execution model), -march=native build.
+  Inside `roofline` the keys that copy figures of [full] legs (hbm_frac, parity_bitwise, sustained_*, e2e_*, configs,
+  hbm_variant) stay null in a plain run.
 
 --dump-outputs DIR: after the timed steps, what the last of them handed back is written to DIR as float64 .npy files (see
 dump_outputs), so that two builds can be compared output for output: the inputs are seeded, the same for the same arguments.
@@ -98,12 +108,16 @@ def parse():
                                                '(tests: the REAL 8-way shard shapes, 64 -> 8 members and 120 -> 15 volumes, at a size eight ranks on one GPU can hold)')
     ap.add_argument('--mask', default='continents', choices=['continents', 'coastline', 'none'],
                     help='c2 land mask: continent-size blobs (default, SURVEY 8(d)), coastline-scale, or none')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
-    ap.add_argument('--no-parity', action='store_true', help='skip the post-run oracle parity check')
-    ap.add_argument('--no-hbm', action='store_true', help='skip the HBM-bound variant')
-    ap.add_argument('--no-configs', action='store_true', help='skip the per-configuration lines')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run every leg that takes runs of its own: '
+                                                        'HBM-bound variant, oracle parity, sustained, per-configuration lines, '
+                                                        'end-to-end, CPU baseline (N = 1, c2)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the cpu_baseline leg')
+    ap.add_argument('--no-parity', action='store_true', help='--full: skip the post-run oracle parity check')
+    ap.add_argument('--no-hbm', action='store_true', help='--full: skip the HBM-bound variant')
+    ap.add_argument('--no-configs', action='store_true', help='--full: skip the per-configuration lines (and the sustained, '
+                                                              'unplanned, mask-sensitivity and contracted legs)')
     ap.add_argument('--inproc', action='store_true', help='also time the in-process multi-device mode (host pointers, ndev = N)')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end (host arrays in, host arrays out) leg')
+    ap.add_argument('--no-e2e', action='store_true', help='--full: skip the end-to-end (host arrays in, host arrays out) leg')
     ap.add_argument('--sustained-seconds', type=float, default=5.0)
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--parity-sweeps', type=int, default=0, help='sweeps of the parity check (0 = the timed count)')
@@ -893,8 +907,10 @@ def main():
         out['roofline'] = roof
 
         single = (world == 1)
+        # --full only: the legs below each take runs of their own and are not needed for the headline figure
+        legs = a.full and a.config == 'c2' and single
         S_res500 = None
-        if a.config == 'c2' and single and not a.no_hbm:
+        if legs and not a.no_hbm:
             # ---- the HBM-bound variant on a working set far beyond the Infinity Cache -----------------
             hm = 8
             ph = c2_problem(a, 0, hm, shared=False)
@@ -948,7 +964,7 @@ def main():
             out['roofline']['hbm_frac'] = out['roofline_hbm']['frac']
             del hb
 
-        if a.config == 'c2' and single and not a.no_parity:
+        if legs and not a.no_parity:
             psw = a.parity_sweeps or sweeps
             rp.reset()
             fl_p, sp_ = rp.solve(psw - 1, 0.0, **opts)
@@ -960,11 +976,11 @@ def main():
             par['same_kernel_config_as_timed'] = bool(same_cfg)
             out['parity'] = par
             out['roofline']['parity_bitwise'] = bool(par['bitwise'] and par['loop_equal'] and same_cfg)
-        if a.config == 'c2' and single and not a.no_configs:
+        if legs and not a.no_configs:
             out['sustained'] = sustained_leg(rp, sweeps, opts, float(nb) * n, a.sustained_seconds)
             out['roofline']['sustained_value'] = out['sustained']['value']
             out['roofline']['sustained_launch_drift'] = out['sustained']['launch_drift']
-        if a.config == 'c2' and single and not a.no_configs:
+        if legs and not a.no_configs:
             # the same solve WITHOUT a resident plan (every call of xinv_<form>_f64_dev re-derives what a plan keeps: what
             # rounds 1-4 timed) -- for continuity with their lines
             rq = ResidentProblem(p, device=local, plan=False)
@@ -973,7 +989,7 @@ def main():
                                 'avg_launch_us': mq / max(lq, 1) * 1e3, 'planned': int(sq.get('planned', 0)),
                                 'note': 'ResidentProblem(plan=False): detection passes, per-row records and tile lists rebuilt in every solve'}
             del rq
-        if a.config == 'c2' and single and a.mask == 'continents' and not a.no_configs:
+        if legs and a.mask == 'continents' and not a.no_configs:
             # mask sensitivity of the headline: the same solve with a coastline-scale mask
             # (few whole tiles to skip) and with tile skipping off
             alt = {}
@@ -985,7 +1001,7 @@ def main():
                             'land_share': float(np.mean(p2['coefs'][3] == p2['undef'])),
                             'avg_launch_us': m2 / max(l2, 1) * 1e3, 'kernel': kernel_name(kind, s2)}
             out['mask_sensitivity'] = alt
-        if a.config == 'c2' and single and not a.no_configs:
+        if legs and not a.no_configs:
             # ---- the opt-in contracted arithmetic (XINV_FLAG_FMA) on the same workload: NOT the headline (the default
             # path is the reference's arithmetic bit for bit); checked bit for bit against the oracle's XO_FMA restatement
             import oracle as orc
@@ -1002,21 +1018,21 @@ def main():
                                  'tied_to_reference': 'tests/test_fma_oracle.py: <= 1e-12 relative to the reference\'s golden '
                                                       'vectors after their sweeps, <= 1e-6 rel-L2 converged'}
         del rp
-        if a.config == 'c2' and single and not a.no_configs:
+        if legs and not a.no_configs:
             out['configs'] = config_lines(local)
             # (the driver's record keeps the contract keys: a compact copy of the table rides inside `roofline`)
             out['roofline']['configs'] = [{k: c.get(k) for k in ('name', 'value', 'members', 'sweeps_per_step', 'kernel', 'bound',
                                                                   'frac', 'valu_frac', 'streamed_frac_of_hbm_peak', 'alg_frac',
                                                                   'traffic_bytes_per_point_sweep', 'traffic_frac_of_hbm_peak',
                                                                   'parity_bitwise')} for c in out['configs']]
-        if a.config == 'c2' and single and not a.no_e2e and (a.ny, a.nx) == (1800, 3600) and a.mask == 'continents':
+        if legs and not a.no_e2e and (a.ny, a.nx) == (1800, 3600) and a.mask == 'continents':
             out['end_to_end'] = end_to_end_leg(local, p, S_res500)
             e2 = out['end_to_end']
             out['roofline'].update({'e2e_c2_invert_poisson_ms': e2['C2_invert_Poisson']['wall_ms'], 'e2e_c5x15_ms': e2['C5x15']['wall_ms'],
                                     'e2e_c5x15_vs_resident': e2['C5x15']['vs_resident'], 'e2e_c4x8_ms': e2['C4x8']['wall_ms']})
         if a.inproc and single:
             out['inproc'] = inproc_leg(a, a.gpus)
-        if a.config == 'c2' and single and not a.no_cpu:
+        if legs and not a.no_cpu:
             out['cpu_baseline'] = cpu_baseline(synthetic.member(p, 0), a.cpu_seconds)
         print(json.dumps(out))
     if joined:

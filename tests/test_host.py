@@ -384,3 +384,16 @@ def test_xarray_edge_round_trip_through_a_standin_module():
         # a Field template, or a bare ndarray, comes back as the Field
         f2 = F.like(vals, 'x')
         assert field.to_like(f2, F) is f2 and field.to_like(f2, vals) is f2
+
+
+# ------------------------------------------------------------------ bench.py options
+def test_bench_extra_legs_are_opt_in(monkeypatch):
+    """A plain `bench.py` run times the headline only; the legs that take runs of their own need --full."""
+    import sys
+    import bench
+    base = ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1']
+    monkeypatch.setattr(sys, 'argv', base)
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', base + ['--full', '--no-cpu'])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu is True and (a.steps, a.warmup) == (3, 1)

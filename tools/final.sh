@@ -15,7 +15,7 @@ if [ "$1" != "noprof" ]; then
 ( time timeout 2400 python -m pytest tests -m gpu -q ) > $out/${RN}_gputests_final.txt 2>&1
 tail -4 $out/${RN}_gputests_final.txt
 fi
-python bench.py 2>$out/bench_err.txt | grep '^{' > $out/${RN}_bench_default.json; python -c "
+python bench.py --full 2>$out/bench_err.txt | grep '^{' > $out/${RN}_bench_default.json; python -c "
 import json; d=json.load(open('$out/${RN}_bench_default.json')); r=d['roofline']
 print('bench default value %.4g active %.4g contracted %.4g ms_per_step %.4f launches x avg %.4f outside %.4f' % (d['value'], d['value_active'], d['contracted']['value'], d['ms_per_step'], r['launches']/d['steps']*r['avg_launch_ms'], r['ms_outside_launches']))
 print(' roofline first keys:', list(r.keys())[:24])
@@ -72,7 +72,7 @@ prof C4 "k_pipe2d<FusedGen2D" "k_pipe2d<Gen2D" 8 2 16588800 python $R/tools/benc
 prof C1 "k_pipe2d<FusedStd2D" "k_pipe2d<Std2D" 1 1 259200 python $R/tools/bench_configs.py c1 --reps 4 --sweeps 500
 prof C5 "k_pipe3d" "k_pipe3d" 15 1 388800000 python $R/tools/bench_configs.py c5 --members 15 --reps 2
 # the headline workload through bench.py itself (kernel trace + traffic of the HBM leg: 8 members in two lanes)
-cmd="python $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity --no-configs --no-e2e"
+cmd="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu --no-parity --no-configs --no-e2e"
 ( cd /tmp; rm -rf /tmp/p_kt /tmp/p_f /tmp/p_w
   rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o r -- $cmd > /dev/null 2>&1
   python $R/tools/prof_summary.py kernels $(db /tmp/p_kt) $out/${RN}_kernel_trace_bench.txt | head -4 | cut -c1-150

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 out=$R/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-cmd="python $R/bench.py --steps 3 --warmup 1 --no-cpu --no-parity --no-configs"
+cmd="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu --no-parity --no-configs"
 db() { find "$1" -name '*.db' | head -1; }
 rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o r -- $cmd > $out/bench_kernel_trace.log 2>&1
 python $R/tools/prof_summary.py kernels $(db /tmp/p_kt) $out/${tag}_kernel_trace_c2.txt
