@@ -479,6 +479,7 @@ struct Pinned {                                     // host ranges registered fo
         if (a2.type != hipMemoryTypeHost) return;
         native.push_back({(char *)h, bytes});
     }
+    void adopt(const void *h, size_t bytes) { try_pin(h, bytes); note_pinned(h, bytes); }    // one host array of the call
     // [h, h + bytes) lies inside a range registered by this call (or by the parent of a per-device call) or inside an
     // array the caller pinned itself: every chunk and member of it copies straight out of / into the caller's memory
     bool covers(const void *h, size_t bytes) const
