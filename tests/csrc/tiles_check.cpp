@@ -7,6 +7,9 @@
 //    slots of one XCD take a contiguous band of the member's tiles; the launch shape xinv_p3_whole_tiles picks is the
 //    cheapest of the three it considers; the 'extend' tiling offset puts the row pairs 0 / 1 and yc-2 / yc-1 into one
 //    wavefront in every row block whose second sweep reads them (checked by laying the rows out, for every row count).
+//  - the planner's cost models: xinv_choose_row_blocks and the k-chunk searches return, for the shipped shapes, what the
+//    planner returned before they moved into the header (recorded tables); every chunk count cuts the column into
+//    non-empty chunks of a multiple of four planes that cover it.
 #include "xinv_tiles.h"
 #include <cstdio>
 #include <vector>
@@ -164,6 +167,157 @@ int main()
                     if (j == yc - 2 && (wave_of(jb, yc - 1) < 0 || wave_of(jb, yc - 1) != wave_of(jb, yc - 2)))
                         return fail("p3 extend: rows yc-2 / yc-1 in two wavefronts", (int)jb, 0, joff, yc);
                 }
+            }
+            cases++;
+        }
+    }
+    // ---- the planner's cost models ----
+    // Expected values recorded from commit 3ddae19 ("Split the host-pointer solve into named steps over one call state"): its
+    // choose_row_blocks (xinv_launch.h) and the two k-chunk loops of plan_fused3d (xinv_plan.h), compiled unchanged into a
+    // scratch harness.  Shapes: 1800x3600, 720x1440, 180x360, 73x144, 2000x2000 (strips of 128 - 4K owned columns, 112 for
+    // the pipelined pass), batches of 1, 8, 64; per row the fifteen results for occ 1..5 x lone 1.0, 1.3, 1.6 (lone runs fastest).
+    {
+        const int occ_cap = 3, pipe_cap = 5, pipe_lag = 7;               // (xinv_launch.h: pipe_occ_cap(); XINV_PIPE_LAG)
+        static const struct { long yc, nstrip, nbatch; int K, pipe; long nrb[15]; } rb[] = {
+            {1800, 30,  1, 1, 0, {34, 34, 34, 34, 68, 68, 34, 68, 68, 34, 68, 68, 34, 68, 68}},
+            {1800, 30,  1, 2, 0, {34, 34, 34, 34, 68, 68, 34, 68, 68, 34, 68, 68, 34, 68, 68}},
+            {1800, 32,  1, 3, 0, {32, 32, 32, 32, 32, 64, 32, 32, 96, 32, 32, 96, 32, 32, 96}},
+            {1800, 33,  1, 4, 0, {31, 31, 31, 31, 62, 62, 31, 62, 62, 31, 62, 62, 31, 62, 62}},
+            {1800, 33,  1, 4, 1, {7, 7, 7, 15, 15, 15, 23, 23, 23, 31, 31, 31, 31, 31, 31}},
+            {1800, 30,  8, 1, 0, {17, 17, 17, 17, 17, 17, 17, 21, 21, 17, 21, 21, 17, 21, 21}},
+            {1800, 30,  8, 2, 0, {21, 21, 21, 21, 17, 17, 21, 21, 21, 21, 21, 21, 21, 21, 21}},
+            {1800, 32,  8, 3, 0, {16, 16, 16, 16, 16, 16, 16, 20, 20, 16, 20, 20, 16, 20, 20}},
+            {1800, 33,  8, 4, 0, {15, 15, 15, 15, 15, 15, 15, 23, 23, 15, 23, 23, 15, 23, 23}},
+            {1800, 33,  8, 4, 1, {12, 12, 12, 11, 11, 11, 11, 11, 11, 11, 11, 11, 9, 9, 9}},
+            {1800, 30, 64, 1, 0, {17, 17, 17, 17, 17, 17, 17, 17, 17, 17, 17, 17, 17, 17, 17}},
+            {1800, 30, 64, 2, 0, {24, 24, 24, 24, 16, 16, 24, 24, 24, 24, 24, 24, 24, 24, 24}},
+            {1800, 32, 64, 3, 0, {17, 17, 17, 17, 17, 17, 17, 15, 15, 17, 15, 15, 17, 15, 15}},
+            {1800, 33, 64, 4, 0, {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            {1800, 33, 64, 4, 1, {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4}},
+            { 720, 12,  1, 1, 0, {85, 85, 85, 85, 85, 170, 85, 85, 170, 85, 85, 170, 85, 85, 170}},
+            { 720, 12,  1, 2, 0, {85, 85, 85, 85, 85, 85, 85, 85, 85, 85, 85, 85, 85, 85, 85}},
+            { 720, 13,  1, 3, 0, {78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78}},
+            { 720, 13,  1, 4, 0, {78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78, 78}},
+            { 720, 13,  1, 4, 1, {19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19, 19}},
+            { 720, 12,  8, 1, 0, {21, 21, 21, 21, 21, 21, 21, 21, 21, 21, 21, 21, 21, 21, 21}},
+            { 720, 12,  8, 2, 0, {10, 10, 10, 10, 21, 21, 10, 21, 21, 10, 21, 21, 10, 21, 21}},
+            { 720, 13,  8, 3, 0, {9, 9, 9, 9, 19, 19, 9, 19, 19, 9, 19, 19, 9, 19, 19}},
+            { 720, 13,  8, 4, 0, {9, 9, 9, 9, 19, 19, 9, 19, 19, 9, 19, 19, 9, 19, 19}},
+            { 720, 13,  8, 4, 1, {2, 2, 2, 4, 4, 4, 7, 7, 7, 7, 7, 7, 12, 12, 12}},
+            { 720, 12, 64, 1, 0, {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8}},
+            { 720, 12, 64, 2, 0, {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8}},
+            { 720, 13, 64, 3, 0, {6, 6, 6, 6, 7, 7, 6, 6, 6, 6, 6, 6, 6, 6, 6}},
+            { 720, 13, 64, 4, 0, {6, 6, 6, 6, 7, 7, 6, 6, 6, 6, 6, 6, 6, 6, 6}},
+            { 720, 13, 64, 4, 1, {4, 4, 4, 3, 3, 3, 4, 4, 4, 2, 2, 2, 3, 3, 3}},
+            { 180,  3,  1, 1, 0, {45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45}},
+            { 180,  3,  1, 2, 0, {45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45}},
+            { 180,  4,  1, 3, 0, {45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45}},
+            { 180,  4,  1, 4, 0, {45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45}},
+            { 180,  4,  1, 4, 1, {45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45, 45}},
+            { 180,  3,  8, 1, 0, {42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42}},
+            { 180,  3,  8, 2, 0, {42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42, 42}},
+            { 180,  4,  8, 3, 0, {32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32}},
+            { 180,  4,  8, 4, 0, {32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32}},
+            { 180,  4,  8, 4, 1, {8, 8, 8, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            { 180,  3, 64, 1, 0, {5, 5, 5, 5, 10, 10, 5, 10, 10, 5, 10, 10, 5, 10, 10}},
+            { 180,  3, 64, 2, 0, {5, 5, 5, 5, 10, 10, 5, 10, 10, 5, 10, 10, 5, 10, 10}},
+            { 180,  4, 64, 3, 0, {4, 4, 4, 4, 8, 8, 4, 8, 8, 4, 8, 8, 4, 8, 8}},
+            { 180,  4, 64, 4, 0, {4, 4, 4, 4, 8, 8, 4, 8, 8, 4, 8, 8, 4, 8, 8}},
+            { 180,  4, 64, 4, 1, {1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 4, 4, 4}},
+    {  73,  2,  1, 1, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  1, 2, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  1, 3, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  1, 4, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  1, 4, 1, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  8, 1, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  8, 2, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  8, 3, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  8, 4, 0, {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 18}},
+    {  73,  2,  8, 4, 1, {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+    {  73,  2, 64, 1, 0, {8, 8, 8, 8, 8, 16, 8, 8, 16, 8, 8, 16, 8, 8, 16}},
+    {  73,  2, 64, 2, 0, {8, 8, 8, 8, 8, 16, 8, 8, 16, 8, 8, 16, 8, 8, 16}},
+    {  73,  2, 64, 3, 0, {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8}},
+    {  73,  2, 64, 4, 0, {8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8}},
+    {  73,  2, 64, 4, 1, {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2}},
+            {2000, 17,  1, 1, 0, {60, 60, 60, 60, 120, 120, 60, 120, 120, 60, 120, 120, 60, 120, 120}},
+            {2000, 17,  1, 2, 0, {60, 60, 60, 60, 120, 120, 60, 120, 120, 60, 120, 120, 60, 120, 120}},
+            {2000, 18,  1, 3, 0, {56, 56, 56, 56, 113, 113, 56, 113, 113, 56, 113, 113, 56, 113, 113}},
+            {2000, 18,  1, 4, 0, {56, 56, 56, 56, 56, 113, 56, 56, 113, 56, 56, 113, 56, 56, 113}},
+            {2000, 18,  1, 4, 1, {14, 14, 14, 28, 28, 28, 42, 42, 42, 56, 56, 56, 56, 56, 56}},
+            {2000, 17,  8, 1, 0, {30, 30, 30, 30, 30, 30, 30, 22, 22, 30, 22, 22, 30, 22, 22}},
+            {2000, 17,  8, 2, 0, {22, 22, 22, 22, 30, 30, 22, 22, 22, 22, 22, 22, 22, 22, 22}},
+            {2000, 18,  8, 3, 0, {21, 21, 21, 21, 28, 28, 21, 21, 21, 21, 21, 21, 21, 21, 21}},
+            {2000, 18,  8, 4, 0, {28, 28, 28, 28, 28, 28, 28, 21, 21, 28, 21, 21, 28, 21, 21}},
+            {2000, 18,  8, 4, 1, {7, 7, 7, 7, 7, 7, 5, 5, 5, 7, 7, 7, 7, 7, 7}},
+            {2000, 17, 64, 1, 0, {16, 16, 16, 16, 16, 30, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            {2000, 17, 64, 2, 0, {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            {2000, 18, 64, 3, 0, {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            {2000, 18, 64, 4, 0, {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16}},
+            {2000, 18, 64, 4, 1, {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4}},
+        };
+        const double lones[3] = {1.0, 1.3, 1.6};
+        for (const auto &r : rb) for (int occ = 1; occ <= 5; occ++) for (int l = 0; l < 3; l++) {
+            const long got = (long)xinv_choose_row_blocks(r.yc, r.nstrip, r.nbatch, r.K, occ, r.pipe ? pipe_cap : occ_cap,
+                                                          lones[l], r.pipe ? pipe_lag : 0);
+            if (got != r.nrb[(occ - 1) * 3 + l]) return fail("row blocks differ from the recorded plan", (int)r.nstrip, (int)got, occ, r.yc);
+            // ... and the cost it was chosen by is the one the masked-tile planner weighs its own splits against
+            const long wgs = (r.nstrip * got + (r.pipe ? 0 : 3)) / (r.pipe ? 1 : 4) * r.nbatch;
+            const double c = xinv_tile_cost(wgs, (r.yc + got - 1) / got, r.K, occ, r.pipe ? pipe_cap : occ_cap, lones[l], r.pipe ? pipe_lag : 0);
+            for (long nr = got + 1; nr <= r.yc / 4; nr++) {              // (ties go to the larger count: none behind it is as cheap)
+                const long w = (r.nstrip * nr + (r.pipe ? 0 : 3)) / (r.pipe ? 1 : 4) * r.nbatch;
+                if (xinv_tile_cost(w, (r.yc + nr - 1) / nr, r.K, occ, r.pipe ? pipe_cap : occ_cap, lones[l], r.pipe ? pipe_lag : 0) <= c)
+                    return fail("a larger row-block count is as cheap", (int)r.nstrip, (int)nr, occ, r.yc);
+            }
+            cases++;
+        }
+        // 50 x 360 x 720 and 601 x 300 x 300, batches of 1, 2, 8, 15, 64: workgroups of k_fused3d with 16 / 12 wavefronts
+        // (wg16, wg12), tiles of k_pipe3d (tiles2) on `cus` compute units -> k chunks of the three
+        static const struct { long zc, wg16, wg12, tiles2; int cus, nk16, nk12, nk2; } kc[] = {
+            { 50,   180,   270,   138,  256, 1, 1, 1},
+            { 50,   180,   270,   138, -256, 1, 1, 1},
+            { 50,   180,   270,   138,   64, 1, 1, 3},
+            { 50,   360,   540,   276,  256, 1, 1, 4},
+            { 50,   360,   540,   276, -256, 1, 1, 1},
+            { 50,   360,   540,   276,   64, 1, 1, 3},
+            { 50,  1440,  2160,  1104,  256, 1, 1, 3},
+            { 50,  1440,  2160,  1104, -256, 1, 1, 1},
+            { 50,  1440,  2160,  1104,   64, 1, 1, 1},
+            { 50,  2700,  4050,  2070,  256, 1, 1, 3},
+            { 50,  2700,  4050,  2070, -256, 1, 1, 1},
+            { 50,  2700,  4050,  2070,   64, 1, 1, 1},
+            { 50, 11520, 17280,  8832,  256, 1, 1, 1},
+            { 50, 11520, 17280,  8832, -256, 1, 1, 1},
+            { 50, 11520, 17280,  8832,   64, 1, 1, 1},
+            {601,    75,   114,    57,  256, 3, 2, 4},
+            {601,    75,   114,    57, -256, 3, 2, 4},
+            {601,    75,   114,    57,   64, 3, 2, 1},
+            {601,   150,   228,   114,  256, 5, 1, 2},
+            {601,   150,   228,   114, -256, 5, 1, 2},
+            {601,   150,   228,   114,   64, 5, 1, 5},
+            {601,   600,   912,   456,  256, 2, 1, 5},
+            {601,   600,   912,   456, -256, 2, 1, 1},
+            {601,   600,   912,   456,   64, 2, 1, 4},
+            {601,  1125,  1710,   855,  256, 2, 1, 2},
+            {601,  1125,  1710,   855, -256, 2, 1, 2},
+            {601,  1125,  1710,   855,   64, 2, 1, 2},
+            {601,  4800,  7296,  3648,  256, 1, 1, 2},
+            {601,  4800,  7296,  3648, -256, 1, 1, 1},
+            {601,  4800,  7296,  3648,   64, 1, 1, 1},
+        };
+        for (const auto &r : kc) {
+            if (xinv_k_chunks_fused3d(r.zc, r.wg16) != r.nk16 || xinv_k_chunks_fused3d(r.zc, r.wg12) != r.nk12)
+                return fail("k chunks (one sweep) differ from the recorded plan", (int)r.wg16, (int)r.wg12, r.cus, r.zc);
+            if (xinv_k_chunks_pipe3d(r.zc, r.tiles2, r.cus) != r.nk2)
+                return fail("k chunks (two sweeps) differ from the recorded plan", (int)r.tiles2, 0, r.cus, r.zc);
+            cases++;
+        }
+        // every chunk count cuts the column into nk non-empty chunks of KC planes, KC a multiple of four, that cover it
+        for (long zc = 3; zc <= 1500; zc++) for (long wgs : {1L, 57L, 138L, 256L, 300L, 2070L, 40000L}) for (int cus : {256, -256, 8}) {
+            for (int which = 0; which < 2; which++) {
+                const int nk = which ? xinv_k_chunks_pipe3d(zc, wgs, cus) : xinv_k_chunks_fused3d(zc, wgs);
+                const long KC = (long)xinv_k_chunk_planes(zc, nk);
+                if (nk < 1 || nk > 16 || KC % 4 != 0 || !((nk - 1) * KC < zc && zc <= nk * KC))
+                    return fail("k chunks do not cut the column", nk, (int)KC, cus, zc);
             }
             cases++;
         }

@@ -21,7 +21,8 @@ struct Plan {
     int64_t srowf2;          // k_pipe3d: member stride of the record table (0: shared by the batch)
     bool bih_zbe;            // biharmonic one-pass kernel: B and E identically zero (terms left out)
     int bih_vm;              // ... where its coefficients come from: 0 per-row records (A..I constant along x), 1 A C D F
-                             // as vector streams + the point-factor stream, 2 all nine (xinv_fusedbih.h); Q in ws->d_pfac
+                             // as vector streams + the point-factor stream, 2 all nine, 3 as 1 with A == C and D == F
+                             // everywhere (two streams less) (xinv_fusedbih.h); Q in ws->d_pfac
     bool aligned;
     unsigned umask;          // fused streams whose rows are constant along x (bit = stream index)
     unsigned um;             // the kernel variant's mask (subset of umask)
@@ -43,8 +44,6 @@ struct Plan {
     bool pq;                 // general form with A, C varying along x: the point-factor stream Q (FusedGen2DQ: relaxation
                              // factor and update predicate of every point, evaluated once per coefficient stack);
                              // Q lives in ws->d_pfac (a plan's own buffer while it solves)
-    bool lag;                // 5-point 2-D kernels: norm + stop rule evaluated by k_norm_reduce_lag on a second stream,
-                             // one pass behind the sweeps (three S buffers); see run_sweeps
 };
 
 // kernel variants instantiated per model: mask of streams read as one scalar per row
@@ -55,6 +54,19 @@ static unsigned pick_um(int kind, unsigned umask)
     if ((umask & 0x1fu) == 0x1fu) return 0x1fu;                                // A, C, D, E, F
     if ((umask & 0x1cu) == 0x1cu) return 0x1cu;                                // D, E, F
     return 0u;
+}
+
+// The streams of the 2-D 5-point kernels: stream q of FusedArgs (and bit q of umask / um above) reads Problem::c[c[q]].
+// Standard form A C F, test form A D E F, general form A C D E F G (B is identically zero on these kernels).
+struct StreamMap {
+    int n, c[6];             // kernel streams; the coefficient each one reads
+    int forcing;             // the stream that is the forcing: the last of every form
+    int nuni;                // leading streams the x-uniform detection looks at (the forcing is not: no variant reads it per row)
+};
+static const StreamMap &stream_map(int kind)
+{
+    static const StreamMap std2d = {3, {0, 2, 3}, 2, 2}, std2dt = {4, {0, 3, 4, 5}, 3, 3}, gen2d = {6, {0, 2, 3, 4, 5, 6}, 5, 5};
+    return kind == KIND_STD2D ? std2d : (kind == KIND_STD2DT ? std2dt : gen2d);
 }
 
 // edge strips whose row blocks are cut in two for a tiling of `nstrip` strips (one strip spans the row: it is both)
@@ -69,11 +81,6 @@ static inline int strip_uw(const Plan &pl, int K, bool pipe)
 
 // k_pipe3d's launch shape (which tiles of a launch march the whole column, which are cut into the plan's k chunks) and the
 // 'extend' variant's tiling offset: xinv_tiles.h (xinv_p3_whole_tiles, xinv_p3_extend_joff; checked on the CPU).
-static int64_t p3_whole_tiles(int64_t tiles, int nk, int64_t KC, int64_t zc, int cus, double *cost_out = nullptr)
-{
-    return xinv_p3_whole_tiles(tiles, nk, KC, zc, cus, cost_out);
-}
-
 static int p3_extend_joff(int64_t yc)
 {
     static_assert(XINV_P3_RR == 3 && XINV_P3_G * XINV_P3_RR - 8 > 0, "k_pipe3d: three rows per wavefront");
@@ -99,8 +106,66 @@ static int fused_dispatch(int kind, bool al, bool ext, unsigned um, int K, dim3 
     return xinv_launch_fused2d_std(al, ext, um, K, grid, block, st, a, occ);
 }
 
-static int pipe_occ_cap();
 static bool ptr_al16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
+// an array a kernel may read as vectors of two doubles: 16-byte aligned, members an even number of elements apart
+static bool vec_aligned(const double *a, int64_t stride) { return ptr_al16(a) && !(stride & 1); }
+
+// Members [member0, member0 + nmem) in launches of at most `chunk` members (grid.y and grid.z are limited to 65535):
+// launch(first member, count) issues one; the first error ends the walk.
+template <class F>
+static int for_member_chunks(int64_t member0, int64_t nmem, F launch, int64_t chunk = XINV_MEMBER_CHUNK)
+{
+    for (int64_t m0 = 0; m0 < nmem; m0 += chunk) {
+        const int rc = launch(member0 + m0, std::min<int64_t>(chunk, nmem - m0));
+        if (rc) return rc;
+    }
+    return XINV_OK;
+}
+
+// BCy = 'extend': the pre-pass of a sweep (numbas.py:87-115) on S of members [member0, member0 + nm), nm <= 65535 --
+// every interior plane of a volume; the biharmonic form has its own.  A no-op for a member that has stopped, unless `force`.
+static void launch_extend(const Problem &p, const Workspace *ws, hipStream_t st, double *S, int force, int64_t member0, int64_t nm)
+{
+    ExtendArgs e;
+    e.S = S; e.sS = p.sS; e.yc = p.yc; e.xc = p.xc;
+    e.kfirst = is3d(p.kind) ? 1 : 0;
+    e.nk = is3d(p.kind) ? p.zc - 2 : 1;
+    // the standard 3-D kernel's second loop stays inside the row (numbas.py:104-108)
+    e.per = (p.BCx == XINV_BC_PERIODIC); e.tall = (p.kind != KIND_STD3D) && (p.yc > p.xc); e.force = force;
+    e.undef = p.sc_.undef; e.ctl = ws->ctl; e.member0 = member0;
+    dim3 g(cdiv(p.xc, 256), (unsigned)e.nk, (unsigned)nm), b(256, 1, 1);
+    if (p.kind == KIND_BIH2D) hipLaunchKernelGGL(k_extend_bih, g, b, 0, st, e);
+    else                      hipLaunchKernelGGL(k_extend, g, b, 0, st, e);
+}
+
+// The buffer behind masked-tile skipping (ws->d_tsum) with `nskip` list slots per member: the skipped tiles' shares of the
+// norm tsum / tcnt [nbatch][nskip], their sums per member xsum / xcnt [nbatch], k_skip_tiles' tickets [nbatch]; `bytes` in all.
+struct TsumPtrs { double *tsum; long long *tcnt; double *xsum; long long *xcnt; unsigned *ticket; size_t bytes; };
+static TsumPtrs tsum_layout(void *buf, int64_t nbatch, int nskip)
+{
+    const size_t nb = (size_t)nbatch, nt = nb * (size_t)nskip, pair = sizeof(double) + sizeof(long long);
+    const uintptr_t base = (uintptr_t)buf;
+    TsumPtrs t;
+    t.tsum = (double *)base;
+    t.tcnt = (long long *)(base + nt * sizeof(double));
+    t.xsum = (double *)(base + nt * pair);
+    t.xcnt = (long long *)(base + nt * pair + nb * sizeof(double));
+    t.ticket = (unsigned *)(base + (nt + nb) * pair);
+    t.bytes = (nt + nb) * pair + nb * sizeof(unsigned);
+    return t;
+}
+
+// Fully masked tiles are left out (plan_tile_skip): the launch runs the listed tiles, `tpw` per workgroup, and takes the
+// skipped tiles' constant share of the norm from xsum / xcnt.  `a` is a FusedArgs / FusedBihArgs.
+template <class A>
+static void set_skip(A &a, const Workspace *ws, const Problem &p, const Plan &pl, int tpw)
+{
+    a.tile_list = ws->d_list;
+    a.ntl = pl.ntl;
+    a.nwg = pl.ntl / tpw;
+    const TsumPtrs t = tsum_layout(ws->d_tsum, p.nbatch, pl.nskip);
+    a.xsum = t.xsum; a.xcnt = t.xcnt;
+}
 
 // Lagged norm (run_sweeps): this launch publishes with `lag_tag` into the partial buffer of its parity;
 // its extra workgroup evaluates `lag_prev`; `lag_out` receives what the evaluation of THIS launch needs.
@@ -124,84 +189,65 @@ static void set_lag(A &a, const Workspace *ws, const Problem &p, int K, unsigned
     }
 }
 
+// What the 5-point and the 9-point launch fill alike: everything of FusedArgs but the coefficient streams, for strips of
+// UW owned columns and four wave-tiles per workgroup.
+static void fused_args(FusedArgs &a, const Problem &p, const Plan &pl, const Workspace *ws, const double *src, double *dst,
+                       int UW, int force, int no_ctl)
+{
+    memset(&a, 0, sizeof a);
+    a.src = src; a.dst = dst; a.sS = p.sS;
+    a.yc = p.yc; a.xc = p.xc;
+    a.per = (p.BCx == XINV_BC_PERIODIC);
+    a.ext = (p.BCy == XINV_BC_EXTEND);
+    a.tall = (p.yc > p.xc);
+    a.RY = pl.even_split ? 0 : pl.RY;
+    a.nstrip = (int)cdiv(p.xc, UW);
+    a.nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
+    a.nwg = (int)cdiv((int64_t)a.nstrip * a.nrb, 4);
+    a.force = force; a.no_ctl = no_ctl;
+    a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
+    a.psum = (unsigned long long *)ws->partials;
+}
+
 static int launch_fused(const Problem &p, const Plan &pl, int K, const double *src, double *dst,
                         Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
                         int no_ctl, unsigned lag_tag = 0, NormLagArgs *lag_out = nullptr,
                         const NormLagArgs *lag_prev = nullptr)
 {
     FusedArgs a;
-    memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst;
-    a.sS = p.sS;
-    if (p.kind == KIND_STD2D) {
-        a.c[0] = p.c[0]; a.sc[0] = p.sc[0];      // A
-        a.c[1] = p.c[2]; a.sc[1] = p.sc[2];      // C
-        a.c[2] = p.c[3]; a.sc[2] = p.sc[3];      // F
-    } else if (p.kind == KIND_STD2DT) {
-        a.c[0] = p.c[0]; a.sc[0] = p.sc[0];      // A
-        for (int q = 3; q < 6; q++) { a.c[q - 2] = p.c[q]; a.sc[q - 2] = p.sc[q]; }   // D, E, F
-    } else {
-        a.c[0] = p.c[0]; a.sc[0] = p.sc[0];      // A
-        for (int q = 2; q < 7; q++) { a.c[q - 1] = p.c[q]; a.sc[q - 1] = p.sc[q]; }   // C..G
-        if (pl.pq) {                             // A, C, D, E, F, Q, G (FusedGen2DQ)
-            a.c[6] = a.c[5]; a.sc[6] = a.sc[5];
-            a.c[5] = (const double *)ws->d_pfac; a.sc[5] = p.yc * p.xc;
-        }
-    }
-    a.yc = p.yc; a.xc = p.xc;
-    a.per = (p.BCx == XINV_BC_PERIODIC);
-    a.ext = (p.BCy == XINV_BC_EXTEND);
-    a.tall = (p.yc > p.xc);
-    a.RY = pl.even_split ? 0 : pl.RY;
     const bool pipe = pl.pipe && K == pl.K;          // wave-pipelined pass: one tile per workgroup
-    const int UW = strip_uw(pl, K, pipe);
-    a.nstrip = (int)cdiv(p.xc, UW);
-    a.nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
-    const int64_t ntiles = (int64_t)a.nstrip * a.nrb;
-    a.nwg = (int)cdiv(ntiles, 4);
-    a.force = force; a.no_ctl = no_ctl;
-    a.member0 = member0;
-    a.sc_ = p.sc_;
-    a.ctl = ws->ctl;
-    a.stop = p.stop;
-    a.psum = (unsigned long long *)ws->partials;
-    if (pipe) { a.nwg = (int)ntiles; a.rowf = ws->d_rowf; }
+    fused_args(a, p, pl, ws, src, dst, strip_uw(pl, K, pipe), force, no_ctl);
+    const StreamMap &sm = stream_map(p.kind);
+    for (int q = 0; q < sm.n; q++) { a.c[q] = p.c[sm.c[q]]; a.sc[q] = p.sc[sm.c[q]]; }
+    if (pl.pq) {                                     // A, C, D, E, F, Q, G (FusedGen2DQ): Q in front of the forcing
+        a.c[sm.forcing + 1] = a.c[sm.forcing]; a.sc[sm.forcing + 1] = a.sc[sm.forcing];
+        a.c[sm.forcing] = (const double *)ws->d_pfac; a.sc[sm.forcing] = p.yc * p.xc;
+    }
+    if (pipe) { a.nwg = a.nstrip * a.nrb; a.rowf = ws->d_rowf; }
 #if XINV_TEST_HOOKS
     a.dbg = (double *)t_hook_record;                 // (run_sweeps: XINV_HOOK_SKIP_PUBLISH; nullptr otherwise)
 #endif
-    if (pl.skip && K == pl.K) {                      // the lists were built for this K's strips
-        a.tile_list = ws->d_list;
-        a.ntl = pl.ntl;
-        a.nwg = pl.ntl / pl.tpw;
-        char *base = (char *)ws->d_tsum;
-        const size_t nt = (size_t)p.nbatch * pl.nskip;
-        a.xsum = (const double *)(base + nt * (sizeof(double) + sizeof(long long)));
-        a.xcnt = (const long long *)(base + nt * (sizeof(double) + sizeof(long long)) + p.nbatch * sizeof(double));
-    }
+    if (pl.skip && K == pl.K) set_skip(a, ws, p, pl, pl.tpw);       // the lists were built for this K's strips
     set_lag(a, ws, p, K, lag_tag, lag_out, lag_prev);
-    for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {      // grid.y is limited to 65535
-        const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-        a.member0 = member0 + m0;
+    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        a.member0 = m;
         dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1), block(256, 1, 1);
         if (pipe) {
             // (XINV_PIPE_LDSPAD: unused dynamic LDS per workgroup, to cap the workgroups per CU in experiments;
             //  capping at the planned count changed nothing: the dispatcher already spreads them evenly)
             const int pad = std::max(0, XINV_ENV_INT("XINV_PIPE_LDSPAD", 0));
             xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.npair, pl.pipe_fr, pl.aligned, a.ext != 0, grid, st, a, nullptr, pad, pl.seam != 0, pl.fma);
-            continue;
+            return XINV_OK;
         }
         if (fused_dispatch(p.kind, pl.aligned, a.ext != 0, pl.um | (pl.alias_ac ? 2u : 0u), K, grid, block, st, a, nullptr, pl.seam != 0, pl.fma, pl.pq))
             return fail_arg("unsupported sweeps_per_launch for this kernel variant");
-    }
+        return XINV_OK;
+    });
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
 
-static int fused9_dispatch(int kind, int K, bool al, bool ext, dim3 grid, hipStream_t st,
-                           const FusedArgs &a, int *occ, bool seam = false)
-{
-    return xinv_launch_fused9(kind == KIND_GEN2D, K, al, ext, grid, st, a, occ, seam);
-}
 // columns a wavefront of the 9-point kernel owns (one halo column per colour and sweep; the seam variants one pair less)
 static inline int strip9_uw(const Plan &pl, int K) { return pl.seam ? xinv_ring_uw(pl.xc, 4 * K) : 128 - 8 * K; }   // (seam: the ring layout, xinv_tiles.h)
 
@@ -211,39 +257,19 @@ static int launch_fused9(const Problem &p, const Plan &pl, int K, const double *
                          const NormLagArgs *lag_prev = nullptr)
 {
     FusedArgs a;
-    memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst; a.sS = p.sS;
+    fused_args(a, p, pl, ws, src, dst, strip9_uw(pl, K), force, no_ctl);
     const int nc = (p.kind == KIND_GEN2D) ? 7 : 4;
     for (int q = 0; q < nc; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
-    a.yc = p.yc; a.xc = p.xc;
-    a.per = (p.BCx == XINV_BC_PERIODIC);
-    a.ext = (p.BCy == XINV_BC_EXTEND);
-    a.tall = (p.yc > p.xc);
-    a.RY = pl.even_split ? 0 : pl.RY;
-    a.nstrip = (int)cdiv(p.xc, strip9_uw(pl, K));
-    a.nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
-    a.nwg = (int)cdiv((int64_t)a.nstrip * a.nrb, 4);
-    a.force = force; a.no_ctl = no_ctl;
-    a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
-    const size_t NBmax = (size_t)pl.nsg;
-    a.psum = (unsigned long long *)ws->partials;
-    if (pl.skip && K == pl.K) {                      // fully masked tiles are left out (plan_tile_skip)
-        a.tile_list = ws->d_list;
-        a.ntl = pl.ntl;
-        a.nwg = pl.ntl / 4;
-        char *base = (char *)ws->d_tsum;
-        const size_t nt = (size_t)p.nbatch * pl.nskip;
-        a.xsum = (const double *)(base + nt * (sizeof(double) + sizeof(long long)));
-        a.xcnt = (const long long *)(base + nt * (sizeof(double) + sizeof(long long)) + p.nbatch * sizeof(double));
-    }
+    if (pl.skip && K == pl.K) set_skip(a, ws, p, pl, 4);
     set_lag(a, ws, p, K, lag_tag, lag_out, lag_prev);
-    for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {
-        const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-        a.member0 = member0 + m0;
+    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        a.member0 = m;
         dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1);
-        if (fused9_dispatch(p.kind, K, pl.aligned, a.ext != 0, grid, st, a, nullptr, pl.seam != 0))
+        if (xinv_launch_fused9(p.kind == KIND_GEN2D, K, pl.aligned, a.ext != 0, grid, st, a, nullptr, pl.seam != 0))
             return fail_arg("unsupported sweeps_per_launch for the 9-point kernel");
-    }
+        return XINV_OK;
+    });
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -258,61 +284,49 @@ static int launch_fused3d(const Problem &p, const Plan &pl, int K, const double 
     for (int q = 0; q < 4; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
     a.zc = p.zc; a.yc = p.yc; a.xc = p.xc;
     a.per = (p.BCx == XINV_BC_PERIODIC);
+    a.force = force; a.no_ctl = no_ctl;
+    a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
+    a.psum = (unsigned long long *)ws->partials;
+    int rc;
     if (K == 2) {                                        // two sweeps per pass: its own tiling
         if (!pl.K2) return fail_arg("internal: two-sweep 3-D pass without its plan");
         a.nstrip = pl.nsg2; a.njb = pl.nrb2; a.joff = pl.joff2;
         a.nkc = std::max(1, pl.nkc2); a.KC = pl.KC2;
-        a.force = force; a.no_ctl = no_ctl;
-        a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
-        a.psum = (unsigned long long *)ws->partials;
+        a.rowf = (const double *)ws->d_rowf; a.srowf = pl.srowf2;
         const int64_t NT2 = (int64_t)a.nstrip * a.njb;
         // a flat grid over the members of the launch (k_pipe3d); at most 2^30 workgroups per launch
         const int64_t mstep = std::max<int64_t>(1, std::min<int64_t>(XINV_MEMBER_CHUNK, ((int64_t)1 << 30) / (NT2 * a.nkc)));
         const bool ext2 = (p.BCy == XINV_BC_EXTEND);
-        for (int64_t m0 = 0; m0 < nmem; m0 += mstep) {
-            const int64_t nm = std::min<int64_t>(mstep, nmem - m0);
-            a.member0 = member0 + m0;
-            a.rowf = (const double *)ws->d_rowf; a.srowf = pl.srowf2;
-            if (ext2) {
-                // 'extend': the pre-pass of the pass's first sweep, in place on the source (numbas.py:87-115; idempotent: a
-                // pass redone from this source by the one-sweep kernel applies it again to the same effect); the second
-                // sweep's is applied inside the kernel (xinv_pipe3d.h: EXT).  A no-op for a member that has stopped.
-                ExtendArgs e;
-                e.S = const_cast<double *>(src); e.sS = p.sS; e.yc = p.yc; e.xc = p.xc;
-                e.kfirst = 1; e.nk = p.zc - 2;
-                e.per = a.per; e.tall = 0; e.force = force;
-                e.undef = p.sc_.undef; e.ctl = ws->ctl; e.member0 = a.member0;
-                for (int64_t q0 = 0; q0 < nm; q0 += 32768) {     // (grid.z is limited to 65535)
-                    const int64_t nq = std::min<int64_t>(32768, nm - q0);
-                    e.member0 = a.member0 + q0;
-                    hipLaunchKernelGGL(k_extend, dim3(cdiv(p.xc, 256), (unsigned)e.nk, (unsigned)nq), dim3(256, 1, 1), 0, st, e);
-                }
-            }
-            // which tiles march the whole column, which are cut into the plan's k chunks (p3_whole_tiles)
-            a.nfull = p3_whole_tiles(NT2 * nm, a.nkc, a.KC, p.zc, pl.cus);
+        rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+            a.member0 = m;
+            // 'extend': the pre-pass of the pass's first sweep, in place on the source (numbas.py:87-115; idempotent: a
+            // pass redone from this source by the one-sweep kernel applies it again to the same effect); the second
+            // sweep's is applied inside the kernel (xinv_pipe3d.h: EXT).  A no-op for a member that has stopped.
+            if (ext2)
+                for_member_chunks(m, nm, [&](int64_t q, int64_t nq) { launch_extend(p, ws, st, const_cast<double *>(src), force, q, nq); return XINV_OK; });
+            // which tiles march the whole column, which are cut into the plan's k chunks (xinv_p3_whole_tiles)
+            a.nfull = xinv_p3_whole_tiles(NT2 * nm, a.nkc, a.KC, p.zc, pl.cus);
             const int64_t nwg = a.nfull + (NT2 * nm - a.nfull) * a.nkc;
             if (pl.fma) xinv_launch_pipe3d_fma(pl.aligned, dim3((unsigned)nwg, 1, 1), st, a);
             else        xinv_launch_pipe3d(pl.aligned, dim3((unsigned)nwg, 1, 1), st, a, pl.seam != 0, ext2);
-        }
-        HIPCHK(hipGetLastError());
-        return XINV_OK;
+            return XINV_OK;
+        }, mstep);
+    } else {
+        a.nstrip = pl.nsg; a.njb = pl.nrb;
+        a.nkc = std::max(1, pl.nkc); a.KC = pl.KC;
+        const size_t NB = (size_t)pl.nsg * pl.nrb * a.nkc;
+        const bool ext = (p.BCy == XINV_BC_EXTEND), uni = (pl.um == 7u);
+        rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+            a.member0 = m;
+            dim3 grid((unsigned)NB, (unsigned)nm, 1);
+            if (pl.seam ? xinv_launch_fused3d_seam(pl.RY, uni, ext, grid, st, a)
+                : pl.fma ? xinv_launch_fused3d_fma(pl.RY, pl.aligned, ext, grid, st, a)
+                         : xinv_launch_fused3d(pl.RY, pl.aligned, uni, ext, grid, st, a))
+                return fail_arg("internal: no 3-D kernel variant for this cross-section");
+            return XINV_OK;
+        });
     }
-    a.nstrip = pl.nsg; a.njb = pl.nrb;
-    a.nkc = std::max(1, pl.nkc); a.KC = pl.KC;
-    a.force = force; a.no_ctl = no_ctl; a.member0 = member0;
-    a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
-    const size_t NB = (size_t)pl.nsg * pl.nrb * a.nkc;
-    a.psum = (unsigned long long *)ws->partials;
-    const bool ext = (p.BCy == XINV_BC_EXTEND), uni = (pl.um == 7u);
-    for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {
-        const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-        a.member0 = member0 + m0;
-        dim3 grid((unsigned)NB, (unsigned)nm, 1);
-        if (pl.seam ? xinv_launch_fused3d_seam(pl.RY, uni, ext, grid, st, a)
-            : pl.fma ? xinv_launch_fused3d_fma(pl.RY, pl.aligned, ext, grid, st, a)
-                     : xinv_launch_fused3d(pl.RY, pl.aligned, uni, ext, grid, st, a))
-            return fail_arg("internal: no 3-D kernel variant for this cross-section");
-    }
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -326,17 +340,8 @@ static int launch_fusedbih(const Problem &p, const Plan &pl, const double *src, 
     const bool per = (p.BCx == XINV_BC_PERIODIC);
     // (prepass = false: finalise() redoing a pass whose source already carries that pass's pre-pass -- the periodic
     //  pre-pass, r0 <- r1 then r1 <- r2, is not idempotent)
-    if (p.BCy == XINV_BC_EXTEND && prepass) {        // the kernel's own pre-pass, on the source buffer
-        ExtendArgs e;
-        e.S = const_cast<double *>(src); e.sS = p.sS; e.yc = p.yc; e.xc = p.xc; e.kfirst = 0; e.nk = 1;
-        e.per = per; e.tall = (p.yc > p.xc); e.force = force;
-        e.undef = p.sc_.undef; e.ctl = ws->ctl;
-        for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {
-            const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-            e.member0 = member0 + m0;
-            hipLaunchKernelGGL(k_extend_bih, dim3(cdiv(p.xc, 256), 1, (unsigned)nm), dim3(256, 1, 1), 0, st, e);
-        }
-    }
+    if (p.BCy == XINV_BC_EXTEND && prepass)          // the kernel's own pre-pass, on the source buffer
+        for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) { launch_extend(p, ws, st, const_cast<double *>(src), force, m, nm); return XINV_OK; });
     FusedBihArgs a;
     memset(&a, 0, sizeof a);
     a.src = src; a.dst = dst; a.sS = p.sS;
@@ -348,25 +353,15 @@ static int launch_fusedbih(const Problem &p, const Plan &pl, const double *src, 
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     a.rowf = (const double *)ws->d_rowf;
     a.q = pl.bih_vm ? (const double *)ws->d_pfac : nullptr;
-    const size_t NBmax = (size_t)pl.nsg;
     a.psum = (unsigned long long *)ws->partials;
-    if (pl.skip) {                                   // fully masked tiles are left out (plan_tile_skip)
-        a.tile_list = ws->d_list;
-        a.ntl = pl.ntl;
-        a.nwg = pl.ntl / 4;
-        char *base = (char *)ws->d_tsum;
-        const size_t nt = (size_t)p.nbatch * pl.nskip;
-        a.xsum = (const double *)(base + nt * (sizeof(double) + sizeof(long long)));
-        a.xcnt = (const long long *)(base + nt * (sizeof(double) + sizeof(long long)) + p.nbatch * sizeof(double));
-    }
+    if (pl.skip) set_skip(a, ws, p, pl, 4);
     set_lag(a, ws, p, 1, lag_tag, lag_out, lag_prev);
-    for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {
-        const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-        a.member0 = member0 + m0;
-        dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1), block(256, 1, 1);
-        (void)block;
+    for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        a.member0 = m;
+        dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1);
         xinv_launch_fusedbih(per, pl.bih_zbe, pl.bih_vm, grid, st, a, nullptr);
-    }
+        return XINV_OK;
+    });
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -383,18 +378,19 @@ static int launch_fused3dg(const Problem &p, const Plan &pl, const double *src, 
     a.per = (p.BCx == XINV_BC_PERIODIC);
     a.nstrip = pl.nsg; a.njb = pl.nrb;
     a.nkc = std::max(1, pl.nkc); a.KC = pl.KC;
-    a.force = force; a.no_ctl = no_ctl; a.member0 = member0;
+    a.force = force; a.no_ctl = no_ctl;
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     const size_t NB = (size_t)pl.nsg * pl.nrb * a.nkc;
     a.psum = (unsigned long long *)ws->partials;
     const bool ext = (p.BCy == XINV_BC_EXTEND);
-    for (int64_t m0 = 0; m0 < nmem; m0 += XINV_MEMBER_CHUNK) {
-        const int64_t nm = std::min<int64_t>(XINV_MEMBER_CHUNK, nmem - m0);
-        a.member0 = member0 + m0;
+    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        a.member0 = m;
         dim3 grid((unsigned)NB, (unsigned)nm, 1);
         if (pl.seam ? xinv_launch_fused3dg_seam(pl.RY, ext, grid, st, a) : xinv_launch_fused3dg(pl.RY, pl.aligned, ext, grid, st, a))
             return fail_arg("internal: no general 3-D kernel variant for this cross-section");
-    }
+        return XINV_OK;
+    });
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -413,14 +409,8 @@ static int launch_colour_chunk(const Problem &p, const Plan &pl, Workspace *ws, 
                                int64_t m0, int64_t nm)
 {
     const int per = (p.BCx == XINV_BC_PERIODIC);
+    if (p.BCy == XINV_BC_EXTEND) launch_extend(p, ws, st, p.S, 0, m0, nm);
     if (p.kind == KIND_BIH2D) {
-        if (p.BCy == XINV_BC_EXTEND) {
-            ExtendArgs e;
-            e.S = p.S; e.sS = p.sS; e.yc = p.yc; e.xc = p.xc; e.kfirst = 0; e.nk = 1;
-            e.per = per; e.tall = (p.yc > p.xc); e.force = 0;
-            e.undef = p.sc_.undef; e.ctl = ws->ctl; e.member0 = m0;
-            hipLaunchKernelGGL(k_extend_bih, dim3(cdiv(p.xc, 256), 1, (unsigned)nm), dim3(256, 1, 1), 0, st, e);
-        }
         ColourArgsBih a;
         memset(&a, 0, sizeof a);
         a.S = p.S; a.sS = p.sS;
@@ -453,19 +443,6 @@ static int launch_colour_chunk(const Problem &p, const Plan &pl, Workspace *ws, 
             if (pl.umask) hipLaunchKernelGGL(k_colour_bih2d<true>, g, b, 0, st, a);
             else          hipLaunchKernelGGL(k_colour_bih2d<false>, g, b, 0, st, a);
         }
-    } else if (p.BCy == XINV_BC_EXTEND) {
-        ExtendArgs e;
-        e.S = p.S; e.sS = p.sS; e.yc = p.yc; e.xc = p.xc;
-        e.kfirst = is3d(p.kind) ? 1 : 0;
-        e.nk = is3d(p.kind) ? p.zc - 2 : 1;
-        // the standard 3-D kernel's second loop stays inside the row (numbas.py:104-108)
-        e.per = per; e.tall = (p.kind != KIND_STD3D) && (p.yc > p.xc); e.force = 0;
-        e.undef = p.sc_.undef; e.ctl = ws->ctl; e.member0 = m0;
-        dim3 g(cdiv(p.xc, 256), (unsigned)e.nk, (unsigned)nm), b(256, 1, 1);
-        hipLaunchKernelGGL(k_extend, g, b, 0, st, e);
-    }
-    if (p.kind == KIND_BIH2D) {
-        // sweeps launched above
     } else if (is3d(p.kind)) {
         ColourArgs3D a;
         memset(&a, 0, sizeof a);
@@ -523,65 +500,66 @@ static int launch_colour_sweep(const Problem &p, const Plan &pl, Workspace *ws, 
     // grid.z carries members (x planes in 3-D) and is limited to 65535
     int64_t chunk = XINV_MEMBER_CHUNK;
     if (is3d(p.kind)) chunk = std::max<int64_t>(1, 65535 / std::max<int64_t>(1, p.zc - 2));
-    for (int64_t m0 = 0; m0 < p.nbatch; m0 += chunk) {
-        int rc = launch_colour_chunk(p, pl, ws, st, m0, std::min<int64_t>(chunk, p.nbatch - m0));
-        if (rc) return rc;
-    }
-    return XINV_OK;
+    return for_member_chunks(0, p.nbatch, [&](int64_t m0, int64_t nm) { return launch_colour_chunk(p, pl, ws, st, m0, nm); }, chunk);
 }
 
-// Number of row blocks for the fused 2-D kernels.  Tall tiles amortise the 4K recomputed halo
-// rows, but every CU should hold the same number of workgroups: `occ` of the chosen variant fit
-// per CU (register-limited, queried from the runtime).  Minimise (workgroups per CU, in rounds of
-// 256*occ resident ones) x (steps per tile); rows are then split evenly over the blocks.
-static int64_t choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int K, int occ, double lone = 1.6,
-                                 bool pipe = false)
-{
-    occ = std::max(1, std::min(occ, pipe ? pipe_occ_cap() : 3));
-    const int64_t cap = 256 * (int64_t)occ, period = pipe ? 4 : 2 * K + 2;
-    int64_t best = 1; double best_cost = 1e300;
-    const int64_t nmin = std::max<int64_t>(1, cdiv(yc, pipe ? 512 : 128)), nmax = std::max<int64_t>(nmin, yc / 4);
-    for (int64_t nr = nmin; nr <= nmax; nr++) {
-        const int64_t rows = cdiv(yc, nr) + 1;                     // +1: even rounding
-        const int64_t steps = pipe ? cdiv(rows + 4 + 3 * XINV_PIPE_LAG, 8) * 8
-                                   : cdiv(rows + 4 * K, period) * period;
-        const int64_t wgs = (int64_t)cdiv(nstrip * nr, pipe ? 1 : 4) * nbatch;
-        // rounds of `cap` resident workgroups; inside a round a CU holds ceil(w/256) of them,
-        // and a lone workgroup on a CU leaves issue slots idle (charged like `lone`: 1.6 for the
-        // issue-bound variants with one or two vector streams, ~1 for the bandwidth-bound ones)
-        const int64_t rounds = cdiv(wgs, cap);
-        const int64_t w_last = wgs - (rounds - 1) * cap;
-        // (pipelined kernel, measured at 3600x1800: a step of n workgroups on a CU costs ~1.5 + n -- 2, 3, 4
-        //  per CU: 0.346, 0.445, 0.543 us -- the wavefronts wait for each other at the step barriers, and more
-        //  of them per SIMD fill the gaps)
-        const double full = pipe ? 1.5 + occ : ((occ == 1) ? lone : (double)occ);
-        const double last = pipe ? 1.5 + (double)cdiv(w_last, 256) : ((w_last <= 256) ? lone : (double)cdiv(w_last, 256));
-        const double cost = ((double)(rounds - 1) * full + last) * (double)steps;
-        if (cost <= best_cost * 1.0001) { best_cost = std::min(cost, best_cost); best = nr; }   // ties: more, shorter tiles
-    }
-    return best;
-}
-
-// Cost of a fused 2-D launch in (workgroups per CU) x (steps per tile) units -- the model behind
-// choose_row_blocks, shared with the masked-tile planner.
-// (pipelined kernel: up to XINV_PIPE_OCC workgroups -- one wavefront each per SIMD -- share a CU)
+// The tiling cost model of the fused 2-D kernels -- xinv_tile_cost, and xinv_choose_row_blocks which minimises it: xinv_tiles.h,
+// checked on the CPU -- with the kernels' constants: at most three workgroups of k_fused2d / k_fused9 per CU count; of the
+// pipelined kernel up to XINV_PIPE_OCC workgroups -- one wavefront each per SIMD -- share a CU.
 static int pipe_occ_cap()
 {
     return std::max(1, XINV_ENV_INT("XINV_PIPE_OCC", 5));
 }
 
-static double tile_cost(int64_t wgs, int64_t rows, int K, int occ, double lone = 1.6, bool pipe = false)
+static double tile_cost(int64_t wgs, int64_t rows, int K, int occ, double lone, bool pipe)
 {
-    occ = std::max(1, std::min(occ, pipe ? pipe_occ_cap() : 3));
-    const int64_t cap = 256 * (int64_t)occ, period = pipe ? 4 : 2 * K + 2;
-    // (pipelined: the last wavefront starts 3 x LAG steps late and enters RY + 4 rows)
-    const int64_t steps = pipe ? cdiv(rows + 1 + 4 + 3 * XINV_PIPE_LAG, 8) * 8
-                               : cdiv(rows + 1 + 4 * K, period) * period;
-    const int64_t rounds = std::max<int64_t>(1, cdiv(wgs, cap));
-    const int64_t w_last = wgs - (rounds - 1) * cap;
-    const double full = pipe ? 1.5 + occ : ((occ == 1) ? lone : (double)occ);
-    const double last = pipe ? 1.5 + (double)cdiv(w_last, 256) : ((w_last <= 256) ? lone : (double)cdiv(w_last, 256));
-    return ((double)(rounds - 1) * full + last) * (double)steps;
+    return xinv_tile_cost(wgs, rows, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0);
+}
+
+static int64_t choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int K, int occ, double lone, bool pipe)
+{
+    return xinv_choose_row_blocks(yc, nstrip, nbatch, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0);
+}
+
+// How many workgroups of the planned kernel variant fit on a CU at K sweeps per pass (register-limited: asked of the
+// runtime through the family's launcher, with zeroed arguments and `occ` set).  *have (when given): the variant exists;
+// where it does not, the answer is the family's default.
+static int plan_occ(const Problem &p, const Plan &pl, hipStream_t st, int K, bool *have = nullptr)
+{
+    const bool ext = (p.BCy == XINV_BC_EXTEND);
+    int occ, missing;
+    if (p.kind == KIND_BIH2D) {
+        FusedBihArgs dummy; memset(&dummy, 0, sizeof dummy);
+        occ = 1;
+        missing = xinv_launch_fusedbih(false, pl.bih_zbe, pl.bih_vm, dim3(1), st, dummy, &occ);
+    } else {
+        FusedArgs dummy; memset(&dummy, 0, sizeof dummy);
+        occ = pl.nine ? 1 : 2;
+        if (pl.nine) missing = xinv_launch_fused9(p.kind == KIND_GEN2D, K, pl.aligned, ext, dim3(1), st, dummy, &occ, pl.seam != 0);
+        else if (pl.pipe) missing = xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.npair, pl.pipe_fr, pl.aligned, ext, dim3(1), st, dummy, &occ, 0, pl.seam != 0, pl.fma);
+        else missing = fused_dispatch(p.kind, pl.aligned, ext, pl.um | (pl.alias_ac ? 2u : 0u), K, dim3(1), dim3(256), st, dummy, &occ, pl.seam != 0, pl.fma, pl.pq);
+    }
+    if (have) *have = !missing;
+    return occ;
+}
+
+// rows_per_tile > 0: tiles of that many rows (rounded up to even); < 0: exactly that many row blocks, split evenly; 0
+// (returns false): the caller's cost model picks the number of row blocks, split_rows_evenly() then.
+static void split_rows_evenly(const Problem &p, Plan &pl, int64_t nrb)
+{
+    pl.nrb = (int)nrb;
+    pl.even_split = true;
+    pl.RY = (int)cdiv(p.yc, pl.nrb);
+}
+static bool rows_per_tile_given(const Problem &p, const xinv_options &opt, Plan &pl)
+{
+    pl.even_split = false;
+    if (opt.rows_per_tile > 0) {
+        pl.RY = (opt.rows_per_tile + 1) & ~1;
+        pl.nrb = (int)cdiv(p.yc, pl.RY);
+    } else if (opt.rows_per_tile < 0)
+        split_rows_evenly(p, pl, std::max<int64_t>(1, std::min<int64_t>(-opt.rows_per_tile, p.yc / 2)));
+    return opt.rows_per_tile != 0;
 }
 
 // Masked-tile skipping for the 5-point fused kernels.  Wave-tiles whose forcing is undefined at
@@ -616,7 +594,7 @@ static int issue_strip_active(const Problem &p, Workspace *ws, hipStream_t st, i
 }
 
 static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t st,
-                          const xinv_options &opt, int fixedRB = 0, int UW_ = 0, int occ_ = 0)
+                          const xinv_options &opt, int fixedRB = 0, int UW_ = 0)
 {
     pl.skip = false; pl.ntl = pl.nskip = 0; pl.skip_pct = 0; pl.skip_ppm = 0;
     const bool forced = (opt.flags & XINV_FLAG_FORCE_TILE_SKIP) != 0;
@@ -630,7 +608,8 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
     const int64_t yc = p.yc, nb = p.nbatch;
     const int64_t cells = yc * nstrip;
     if (nb * nstrip * (yc + 1) > (int64_t)50000000) return XINV_OK;   // host-side prefix table would exceed 200 MB
-    const int fi = (p.kind == KIND_STD2D) ? 3 : (p.kind == KIND_GEN2D ? 6 : (p.kind == KIND_BIH2D ? 9 : 5));   // the forcing
+    const StreamMap &sm = stream_map(p.kind);
+    const int fi = (p.kind == KIND_BIH2D) ? 9 : sm.c[sm.forcing];      // the forcing (biharmonic form: J, the last of its ten arrays)
 
     int rc = XINV_OK;
     if (!(ws->act_ready && ws->act_uw == UW && ws->act_f == p.c[fi])) {     // (not already there: issue_strip_active below)
@@ -690,12 +669,7 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
         if (maxact) *maxact = mx;
         return wgs;
     };
-    int occ = occ_ > 0 ? occ_ : 2;
-    if (!fixedRB && occ_ <= 0) {
-        FusedArgs dummy; memset(&dummy, 0, sizeof dummy);
-        if (pl.pipe) xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.npair, pl.pipe_fr, pl.aligned, ext, dim3(1), st, dummy, &occ, 0, pl.seam != 0, pl.fma);
-        else fused_dispatch(p.kind, pl.aligned, ext, pl.um | (pl.alias_ac ? 2u : 0u), K, dim3(1), dim3(256), st, dummy, &occ, pl.seam != 0, pl.fma, pl.pq);
-    }
+    const int occ = fixedRB ? 2 : plan_occ(p, pl, st, K);
     const bool pp = pl.pipe;
     const double cost0 = tile_cost((int64_t)cdiv((int64_t)nstrip * pl.nrb, tpw) * nb, cdiv(yc, pl.nrb), K, occ, pl.lone, pp);
     // candidates: the row split that brings the ACTIVE workgroups back to the default count sits
@@ -763,27 +737,21 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
         for (int t = 0; t < nskip; t++) hs[m * nskip + t] = t < (int)skp[(size_t)m].size() ? skp[(size_t)m][t] : -1;
     }
     HIPCHK(hipMemcpyAsync(ws->d_list, ws->h_list, nints * sizeof(int), hipMemcpyHostToDevice, st));
-    const size_t nt = (size_t)nb * nskip;
-    const size_t tsum_bytes = (nt + (size_t)nb) * (sizeof(double) + sizeof(long long));
-    rc = ensure_dev(&ws->d_tsum, &ws->d_tsum_cap, tsum_bytes + (size_t)nb * sizeof(unsigned));
+    rc = ensure_dev(&ws->d_tsum, &ws->d_tsum_cap, tsum_layout(nullptr, nb, nskip).bytes);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync((char *)ws->d_tsum + tsum_bytes, 0, (size_t)nb * sizeof(unsigned), st));   // k_skip_tiles' tickets
+    const TsumPtrs ts = tsum_layout(ws->d_tsum, nb, nskip);
+    HIPCHK(hipMemsetAsync(ts.ticket, 0, (size_t)nb * sizeof(unsigned), st));   // k_skip_tiles' tickets
     SkipNormArgs na;
     na.S = p.S; na.sS = p.sS; na.yc = yc; na.xc = p.xc; na.nstrip = nstrip; na.nrb = best; na.UW = UW; na.RB = fixedRB;
     na.undef = p.sc_.undef; na.skip_list = ws->d_list + (size_t)nb * ntl; na.nskip_max = nskip;
-    char *base = (char *)ws->d_tsum;
-    na.tsum = (double *)base;
-    na.tcnt = (long long *)(base + nt * sizeof(double));
-    na.xsum = (double *)(base + nt * (sizeof(double) + sizeof(long long)));
-    na.xcnt = (long long *)(base + nt * (sizeof(double) + sizeof(long long)) + (size_t)nb * sizeof(double));
-    na.ticket = (unsigned *)(base + tsum_bytes);
+    na.tsum = ts.tsum; na.tcnt = ts.tcnt; na.xsum = ts.xsum; na.xcnt = ts.xcnt; na.ticket = ts.ticket;
     pl.skipna = na;                                      // (the skipped tiles' norm share and their copies: run_sweeps)
 
     pl.skip = true; pl.ntl = ntl; pl.nskip = nskip;
     pl.skip_pct = (int)((100 * nskipped) / (ntiles * nb));
     pl.skip_ppm = (int)((1000000 * nskipped) / (ntiles * nb));
     if (!fixedRB) {
-        pl.nrb = best; pl.even_split = true; pl.RY = (int)cdiv(yc, best);
+        split_rows_evenly(p, pl, best);
         pl.nsg = (int)cdiv((int64_t)cdiv(p.xc, 128 - (pl.nine ? 8 : 4) * XINV_KMAX - (pl.seam ? 4 : 0)) * pl.nrb, pl.pipe ? 4 : tpw) + 1;
         if (pl.pipe) pl.nsg = std::max(pl.nsg, (int)cdiv(p.xc, UW) * pl.nrb + 1);
     }

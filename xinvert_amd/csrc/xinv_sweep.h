@@ -157,7 +157,7 @@ static void plan_stats(const Problem &p, const Plan &pl, int lanes, int64_t laun
         t_stats.k_chunks = std::max(1, pl.nkc2);
         const int64_t tiles = (int64_t)pl.nsg2 * pl.nrb2 * launch_members;
         if (launch_members > 0)
-            t_stats.cut_tiles = (int32_t)(tiles - p3_whole_tiles(tiles, std::max(1, pl.nkc2), pl.KC2, p.zc, pl.cus));
+            t_stats.cut_tiles = (int32_t)(tiles - xinv_p3_whole_tiles(tiles, std::max(1, pl.nkc2), pl.KC2, p.zc, pl.cus));
     }
 }
 

@@ -1,4 +1,5 @@
-// xinv_tiles.h -- tile ids of the 2-D streaming kernels (k_fused2d / k_pipe2d) and the dispatch order of seam launches:
+// xinv_tiles.h -- tile ids of the 2-D streaming kernels (k_fused2d / k_pipe2d), the dispatch order of seam launches and the
+// planner's tiling cost models:
 // integer arithmetic shared by the kernels and the planner (xinv_launch.h), and compiled on its own by the CPU suite
 // (tests/test_tiles.py builds tests/csrc/tiles_check.cpp with g++ against this header).
 #pragma once
@@ -163,4 +164,81 @@ __host__ __device__ inline bool xinv_p3_extend_ok(int64_t yc, int joff, int RJ, 
 __host__ __device__ inline int xinv_p3_extend_joff(int64_t yc, int RJ, int H, int RR)
 {
     return xinv_p3_extend_ok(yc, 0, RJ, H, RR) ? 0 : (xinv_p3_extend_ok(yc, 2, RJ, H, RR) ? 2 : -1);
+}
+
+// ---- the planner's cost models (host only; pure integer / double arithmetic, checked on the CPU) --------------------------
+__host__ inline int64_t xinv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Cost of a fused 2-D launch of `wgs` workgroups whose tiles own `rows` rows, in (workgroups per CU) x (steps per tile)
+// units: the model behind xinv_choose_row_blocks, shared with the masked-tile planner.  `occ` workgroups of the variant
+// fit per CU (register-limited, queried from the runtime), of which the model counts at most `occ_cap`.
+// `pipe_lag` > 0: the wave-pipelined pass (k_pipe2d: one tile per workgroup; pipe_lag = steps wavefront p+1 runs behind
+// wavefront p -- the last wavefront starts 3 x pipe_lag steps late and enters rows + 4 rows); 0: k_fused2d / k_fused9 at K
+// sweeps per pass.
+__host__ inline double xinv_tile_cost(int64_t wgs, int64_t rows, int K, int occ, int occ_cap, double lone, int pipe_lag)
+{
+    const bool pipe = pipe_lag > 0;
+    occ = occ < occ_cap ? occ : occ_cap;
+    occ = occ > 1 ? occ : 1;
+    const int64_t cap = 256 * (int64_t)occ, period = pipe ? 4 : 2 * K + 2;
+    const int64_t steps = pipe ? xinv_cdiv(rows + 1 + 4 + 3 * pipe_lag, 8) * 8               // +1: even rounding
+                               : xinv_cdiv(rows + 1 + 4 * K, period) * period;
+    // rounds of `cap` resident workgroups; inside a round a CU holds ceil(w/256) of them,
+    // and a lone workgroup on a CU leaves issue slots idle (charged like `lone`: 1.6 for the
+    // issue-bound variants with one or two vector streams, ~1 for the bandwidth-bound ones)
+    const int64_t r = xinv_cdiv(wgs, cap), rounds = r > 1 ? r : 1;
+    const int64_t w_last = wgs - (rounds - 1) * cap;
+    // (pipelined kernel, measured at 3600x1800: a step of n workgroups on a CU costs ~1.5 + n -- 2, 3, 4
+    //  per CU: 0.346, 0.445, 0.543 us -- the wavefronts wait for each other at the step barriers, and more
+    //  of them per SIMD fill the gaps)
+    const double full = pipe ? 1.5 + occ : ((occ == 1) ? lone : (double)occ);
+    const double last = pipe ? 1.5 + (double)xinv_cdiv(w_last, 256) : ((w_last <= 256) ? lone : (double)xinv_cdiv(w_last, 256));
+    return ((double)(rounds - 1) * full + last) * (double)steps;
+}
+
+// Number of row blocks for the fused 2-D kernels.  Tall tiles amortise the 4K recomputed halo
+// rows, but every CU should hold the same number of workgroups: `occ` of the chosen variant fit
+// per CU.  Minimise (workgroups per CU, in rounds of 256*occ resident ones) x (steps per tile): xinv_tile_cost;
+// rows are then split evenly over the blocks.
+__host__ inline int64_t xinv_choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int K, int occ, int occ_cap,
+                                               double lone, int pipe_lag)
+{
+    const bool pipe = pipe_lag > 0;
+    int64_t best = 1; double best_cost = 1e300;
+    const int64_t n0 = xinv_cdiv(yc, pipe ? 512 : 128), nmin = n0 > 1 ? n0 : 1, nmax = nmin > yc / 4 ? nmin : yc / 4;
+    for (int64_t nr = nmin; nr <= nmax; nr++) {
+        const int64_t wgs = xinv_cdiv(nstrip * nr, pipe ? 1 : 4) * nbatch;
+        const double cost = xinv_tile_cost(wgs, xinv_cdiv(yc, nr), K, occ, occ_cap, lone, pipe_lag);
+        if (cost <= best_cost * 1.0001) { best_cost = cost < best_cost ? cost : best_cost; best = nr; }   // ties: more, shorter tiles
+    }
+    return best;
+}
+
+// The cut of a 3-D column of zc planes into k chunks: nk chunks of KC = xinv_k_chunk_planes(zc, nk) planes (a multiple of
+// four, at least 16, no empty chunk), nk <= 16; the count whose launch cost(nk, KC) is lowest, more chunks only for a gain
+// of 3 %.
+__host__ inline int64_t xinv_k_chunk_planes(int64_t zc, int nk) { return xinv_cdiv(xinv_cdiv(zc, nk), 4) * 4; }
+template <class Cost>
+__host__ inline int xinv_choose_k_chunks(int64_t zc, Cost cost)
+{
+    int best = 1; double best_cost = 1e300;
+    for (int nk = 1; nk <= 16; nk++) {
+        const int64_t KC = xinv_k_chunk_planes(zc, nk);
+        if (nk > 1 && (KC < 16 || (int64_t)(nk - 1) * KC >= zc)) break;
+        const double c = cost(nk, KC);
+        if (c < best_cost * 0.97) { best_cost = c; best = nk; }
+    }
+    return best;
+}
+// k_fused3d / k_fused3dg (`wgs` = strips x row blocks x members): one workgroup per CU is resident (16 / 12 waves); the
+// chunk count that minimises (rounds of 256 workgroups) x (planes marched per workgroup, incl. 4 halo + 4 warm-up)
+__host__ inline int xinv_k_chunks_fused3d(int64_t zc, int64_t wgs)
+{
+    return xinv_choose_k_chunks(zc, [&](int nk, int64_t KC) { return (double)xinv_cdiv(wgs * nk, 256) * (double)(KC + (nk > 1 ? 10 : 2)); });
+}
+// k_pipe3d (xinv_p3_whole_tiles: which tiles of a launch are cut is decided per launch): the count that makes the launch
+// of the whole batch (`tiles` = strips x row blocks x members) cheapest
+__host__ inline int xinv_k_chunks_pipe3d(int64_t zc, int64_t tiles, int cus)
+{
+    return xinv_choose_k_chunks(zc, [&](int nk, int64_t KC) { double c; xinv_p3_whole_tiles(tiles, nk, KC, zc, cus, &c); return c; });
 }
