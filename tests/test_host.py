@@ -28,6 +28,93 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert (so.value, ss.value) == (ctypes.sizeof(_lib.XinvOptions), ctypes.sizeof(_lib.XinvStats))
 
 
+def _header_prototypes():
+    """{name: [(C type, parameter name)]} of every `int xinv_...(...);` of include/xinv.h."""
+    hdr = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'xinv.h')).read(), flags=re.S)
+    protos = {}
+    for name, plist in re.findall(r'\bint\s+(xinv_\w+)\s*\(([^)]*)\)\s*;', hdr):
+        ps = []
+        for par in plist.split(','):
+            m = re.fullmatch(r'\s*(.*?)(\w+)\s*', par, flags=re.S)
+            ps.append((' '.join(m.group(1).replace('*', ' * ').split()).replace('* *', '**'), m.group(2)))
+        protos[name] = ps
+    return protos
+
+
+def test_forms_table_matches_the_header():
+    """xinvert_amd/forms.py is the one restatement of the forms' argument lists: every entry point it describes is a
+    prototype of include/xinv.h with the same parameter names in the same order and matching C types."""
+    import ctypes
+    from xinvert_amd import forms
+    protos = _header_prototypes()
+    assert len(protos) == 40
+    dp = ctypes.POINTER(ctypes.c_double)
+    ctype_of = {'double *': (dp, ctypes.c_void_p), 'const double *': (dp, ctypes.c_void_p),
+                'int64_t': (ctypes.c_int64,), 'double': (ctypes.c_double,), 'int': (ctypes.c_int,),
+                'const int64_t *': (ctypes.POINTER(ctypes.c_int64),),
+                'const xinv_options *': (ctypes.POINTER(_lib.XinvOptions),), 'void *': (ctypes.c_void_p,),
+                'xinv_plan **': (ctypes.POINTER(ctypes.c_void_p),)}
+    seen = set()
+    for kind, f in forms.FORMS.items():
+        for entry in ('single', 'batched', 'dev', 'plan'):
+            if entry == 'plan' and kind == 'std1d':               # the 1-D form has no plan entry, here or in the header
+                with pytest.raises(KeyError):
+                    forms.symbol(kind, entry)
+                assert not any('plan_create' in n and '1d' in n for n in protos)
+                continue
+            name = forms.symbol(kind, entry)
+            assert name in protos, name
+            seen.add(name)
+            assert [n for _, n in protos[name]] == [n for n, _ in forms.params(kind, entry)], name
+            at = forms.argtypes(kind, entry)
+            assert len(at) == len(protos[name])
+            for (ctype, pname), t in zip(protos[name], at):
+                assert t in ctype_of[ctype], (name, pname, ctype, t)
+    # ... and the header has no form the table does not know: what is left are the entries _lib.load() types by hand
+    assert set(protos) - seen == {
+        'xinv_last_stats', 'xinv_device_count', 'xinv_version', 'xinv_gm_flow_f64_dev', 'xinv_abs_norm_f64_dev',
+        'xinv_fd_f64', 'xinv_fd_f64_dev', 'xinv_mg_restrict_f64_dev', 'xinv_mg_prolong_f64_dev',
+        'xinv_plan_solve_f64_dev', 'xinv_plan_solve_frames_f64_dev', 'xinv_plan_refresh', 'xinv_plan_destroy'}
+    assert len(seen) == 27
+    # the library's own table (xinv_host.h: FORM[kind] = { ncoef, rank, null_B, stop_on_zero_norm }) says the same
+    host = open(os.path.join(ROOT, 'xinvert_amd', 'csrc', 'xinv_host.h')).read()
+    rows = re.findall(r'/\* KIND_(\w+)\s*\*/ \{ (\d+), (\d+), (\d+), (\d+) \}', host)
+    assert sorted(k.lower() for k, *_ in rows) == sorted(k for k in forms.FORMS if k != 'std1d')
+    for k, ncoef, rank, null_B, zero_stop in rows:
+        f = forms.FORMS[k.lower()]
+        assert (int(ncoef), int(rank), bool(int(null_B))) == (len(f.arrays), f.rank, f.null_B), k
+        assert int(zero_stop) == (k in ('STD2D', 'STD2DT')), k
+
+
+def test_forms_scalars_from_iparams_keep_the_front_ends_order():
+    """from_iparams + scalars give, form by form, the positional list core._solve spelt out by hand before the table
+    (written out here from that code: gc2, gc1, del2, del1, BCs[0], BCs[1], del1Sqr, ...)."""
+    from xinvert_amd import forms
+    ip = dict(gc1=11, gc2=9, gc3=5, del1=1.5, del2=2.5, del3=3.5, del1Sqr=4.5, del1SSr=5.5, del1Tr=6.5, ratio=7.5,
+              ratioQtr=8.5, ratioSqr=9.5, ratioSSr=10.5, ratio1=11.5, ratio2=12.5, ratio1Sqr=13.5, ratio2Sqr=14.5,
+              optArg=15.5, BCs=['extend', 'periodic', 'fixed'], mxLoop=3, tolerance=1e-9)
+    U = -9.99e8
+    want = {
+        'std1d': [11, 1.5, 1, 4.5, 15.5, U],
+        'std2d': [9, 11, 2.5, 1.5, 1, 2, 4.5, 8.5, 9.5, 15.5, U],
+        'gen2d': [9, 11, 2.5, 1.5, 1, 2, 4.5, 7.5, 8.5, 9.5, 15.5, U],
+        'std2dt': [9, 11, 2.5, 1.5, 1, 2, 4.5, 8.5, 9.5, 15.5, U],
+        'bih2d': [9, 11, 2.5, 1.5, 1, 2, 5.5, 6.5, 4.5, 7.5, 10.5, 8.5, 9.5, 15.5, U],
+        'std3d': [5, 9, 11, 3.5, 2.5, 1.5, 1, 2, 0, 4.5, 14.5, 13.5, 15.5, U],
+        'gen3d': [5, 9, 11, 3.5, 2.5, 1.5, 1, 2, 0, 4.5, 12.5, 11.5, 14.5, 13.5, 15.5, U],
+    }
+    assert set(want) == set(forms.FORMS)
+    for kind, w in want.items():
+        p = forms.from_iparams(kind, ip, U)
+        got = forms.scalars(p)
+        assert got == w and [type(v) for v in got] == [type(v) for v in w], (kind, got)
+        assert p['kind'] == kind and len(got) == len(forms.FORMS[kind].scalars)
+    # what the front end and the resident batch look up by name
+    assert core._KIND_OF == {'inv_standard2D': 'std2d', 'inv_standard2D_test': 'std2dt', 'inv_general2D': 'gen2d',
+                             'inv_general2D_bih': 'bih2d', 'inv_standard3D': 'std3d', 'inv_general3D': 'gen3d'}
+    assert all(hasattr(core, f.inv) for f in forms.FORMS.values())
+
+
 def test_shipped_library_does_not_import_getenv():
     """no environment switch alters a production solve -- the shipped shared object does not even import
     getenv (the planner's overrides are xinv_options fields; only the test-hooks / experiment builds read XINV_*)."""

@@ -4,6 +4,8 @@ import os
 
 import numpy as np
 
+from xinvert_amd import _lib, forms
+
 U = -9.99e8
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -152,66 +154,20 @@ def run_oracle(p, mxLoop, tol, order):
     S = np.array(p['S0'], dtype=np.float64, copy=True)
     fl = np.array([0., 1., 0.])
     c = [np.ascontiguousarray(a, dtype=np.float64) for a in p['coefs']]
-    if p['kind'] == 'std2d':
-        orc.standard_2d(S, *c, p['yc'], p['xc'], p['dely'], p['delx'], p['BCy'], p['BCx'],
-                        p['delxSqr'], p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef'], fl,
-                        mxLoop, tol, order)
-    elif p['kind'] == 'gen2d':
-        orc.general_2d(S, *c, p['yc'], p['xc'], p['dely'], p['delx'], p['BCy'], p['BCx'],
-                       p['delxSqr'], p['ratio'], p['ratioQtr'], p['ratioSqr'], p['optArg'],
-                       p['undef'], fl, mxLoop, tol, order)
-    elif p['kind'] == 'std2dt':
-        orc.standard_2d_test(S, *c, p['yc'], p['xc'], p['dely'], p['delx'], p['BCy'], p['BCx'],
-                             p['delxSqr'], p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef'], fl,
-                             mxLoop, tol, order)
-    elif p['kind'] == 'bih2d':
-        orc.general_bih_2d(S, *c, p['yc'], p['xc'], p['dely'], p['delx'], p['BCy'], p['BCx'],
-                           p['delxSSr'], p['delxTr'], p['delxSqr'], p['ratio'], p['ratioSSr'],
-                           p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef'], fl, mxLoop, tol,
-                           order)
-    elif p['kind'] == 'gen3d':
-        orc.general_3d(S, *c, p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'],
-                       p['BCz'], p['BCy'], p['BCx'], p['delxSqr'], p['ratio2'], p['ratio1'],
-                       p['ratio2Sqr'], p['ratio1Sqr'], p['optArg'], p['undef'], fl, mxLoop, tol, order)
-    else:
-        orc.standard_3d(S, *c, p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'],
-                        p['BCz'], p['BCy'], p['BCx'], p['delxSqr'], p['ratio2Sqr'], p['ratio1Sqr'],
-                        p['optArg'], p['undef'], fl, mxLoop, tol, order)
+    getattr(orc, forms.FORMS[p['kind']].name)(S, *c, *forms.scalars(p), fl, mxLoop, tol, order)
     return S, fl
 
 
 # ------------------------------------------------------------------ HIP runners (C-ABI)
 def _scal(p, flags, mxLoop, tol):
-    from xinvert_amd import _lib
-    b = _lib.bc
-    fp = _lib.hptr(flags)
-    if p['kind'] in ('std2d', 'std2dt'):
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSqr'],
-                p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef'], fp, mxLoop, tol]
-    if p['kind'] == 'gen2d':
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSqr'],
-                p['ratio'], p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef'], fp, mxLoop, tol]
-    if p['kind'] == 'bih2d':
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSSr'],
-                p['delxTr'], p['delxSqr'], p['ratio'], p['ratioSSr'], p['ratioQtr'], p['ratioSqr'],
-                p['optArg'], p['undef'], fp, mxLoop, tol]
-    if p['kind'] == 'gen3d':
-        return [p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'], b(p['BCz']), b(p['BCy']),
-                b(p['BCx']), p['delxSqr'], p['ratio2'], p['ratio1'], p['ratio2Sqr'], p['ratio1Sqr'],
-                p['optArg'], p['undef'], fp, mxLoop, tol]
-    return [p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'], b(p['BCz']), b(p['BCy']),
-            b(p['BCx']), p['delxSqr'], p['ratio2Sqr'], p['ratio1Sqr'], p['optArg'], p['undef'],
-            fp, mxLoop, tol]
+    return forms.scalars(p) + [_lib.hptr(flags), mxLoop, tol]
 
 
-_FN = {'std2d': 'xinv_standard_2d_f64', 'gen2d': 'xinv_general_2d_f64', 'std3d': 'xinv_standard_3d_f64',
-       'bih2d': 'xinv_general_bih_2d_f64', 'std2dt': 'xinv_standard_2d_test_f64',
-       'gen3d': 'xinv_general_3d_f64'}
+_FN = {k: forms.symbol(k, 'single') for k in forms.FORMS}
 
 
 def run_hip_single(p, mxLoop, tol):
     """The positional single-slice twin of the numba kernel (host pointers)."""
-    from xinvert_amd import _lib
     L = _lib.require_gpu()
     S = np.array(p['S0'], dtype=np.float64, copy=True)
     fl = np.array([0., 1., 0.])
@@ -224,7 +180,6 @@ def run_hip_single(p, mxLoop, tol):
 def run_hip_batched(ps, mxLoop, tol, shared=(), **opt):
     """Host-pointer batched entry.  `ps`: list of problems of identical geometry; coefficient
     indices in `shared` are passed once with batch stride 0."""
-    from xinvert_amd import _lib
     L = _lib.require_gpu()
     p = ps[0]
     nb = len(ps)
@@ -249,7 +204,6 @@ def run_hip_batched(ps, mxLoop, tol, shared=(), **opt):
 def run_hip_dev(ps, mxLoop, tol, shared=(), stream=None, **opt):
     """Device-pointer batched entry with torch-owned HBM buffers."""
     import torch
-    from xinvert_amd import _lib
     L = _lib.require_gpu()
     p = ps[0]
     nb = len(ps)

@@ -3,6 +3,7 @@
 Layout (only what the hot path needs):
   csrc/          hand-written HIP kernels for gfx950 + the C-ABI (include/xinv.h)
   _lib.py        ctypes binding of libxinv_hip.so (no CPU fallback)
+  forms.py       the operator forms as one table: symbols, arrays, scalar order (what _lib, core and resident share)
   core.py        inv_standard1D / inv_standard2D / inv_general2D / inv_standard3D / inv_general3D ...   (reference xinvert/core.py)
   apps.py        invert_Poisson / invert_Stommel / invert_GillMatsuno / invert_omega, cal_flow
                  (reference xinvert/apps.py)

@@ -104,37 +104,11 @@ def load():
     except OSError as e:
         raise XinvError('cannot load %s: %s' % (SO, e))
     _opt = ctypes.POINTER(XinvOptions)
-    std2d_scal = [_i64, _i64, _f64, _f64, _int, _int, _f64, _f64, _f64, _f64, _f64, _dp, _i64, _f64]
-    gen2d_scal = [_i64, _i64, _f64, _f64, _int, _int, _f64, _f64, _f64, _f64, _f64, _f64, _dp, _i64, _f64]
-    std3d_scal = [_i64, _i64, _i64, _f64, _f64, _f64, _int, _int, _int, _f64, _f64, _f64, _f64,
-                  _f64, _dp, _i64, _f64]
-    L.xinv_standard_2d_f64.argtypes = [_dp] * 5 + std2d_scal
-    L.xinv_general_2d_f64.argtypes = [_dp] * 8 + gen2d_scal
-    L.xinv_standard_3d_f64.argtypes = [_dp] * 5 + std3d_scal
-    L.xinv_standard_2d_f64_batched.argtypes = [_dp] * 5 + [_i64, _ip] + std2d_scal + [_opt]
-    L.xinv_general_2d_f64_batched.argtypes = [_dp] * 8 + [_i64, _ip] + gen2d_scal + [_opt]
-    L.xinv_standard_3d_f64_batched.argtypes = [_dp] * 5 + [_i64, _ip] + std3d_scal + [_opt]
-    # *_dev: array arguments are device addresses (integers), flags is a host pointer
-    std2d_dev = [_i64, _i64, _f64, _f64, _int, _int, _f64, _f64, _f64, _f64, _f64, _dp, _i64, _f64]
-    L.xinv_standard_2d_f64_dev.argtypes = [_vp] * 5 + [_i64, _ip] + std2d_dev + [_opt, _vp]
-    L.xinv_general_2d_f64_dev.argtypes = [_vp] * 8 + [_i64, _ip] + gen2d_scal + [_opt, _vp]
-    L.xinv_standard_3d_f64_dev.argtypes = [_vp] * 5 + [_i64, _ip] + std3d_scal + [_opt, _vp]
-    bih_scal = [_i64, _i64, _f64, _f64, _int, _int] + [_f64] * 9 + [_dp, _i64, _f64]
-    L.xinv_general_bih_2d_f64.argtypes = [_dp] * 11 + bih_scal
-    L.xinv_general_bih_2d_f64_batched.argtypes = [_dp] * 11 + [_i64, _ip] + bih_scal + [_opt]
-    L.xinv_general_bih_2d_f64_dev.argtypes = [_vp] * 11 + [_i64, _ip] + bih_scal + [_opt, _vp]
-    L.xinv_standard_2d_test_f64.argtypes = [_dp] * 7 + std2d_scal
-    L.xinv_standard_2d_test_f64_batched.argtypes = [_dp] * 7 + [_i64, _ip] + std2d_scal + [_opt]
-    L.xinv_standard_2d_test_f64_dev.argtypes = [_vp] * 7 + [_i64, _ip] + std2d_scal + [_opt, _vp]
-    gen3d_scal = [_i64, _i64, _i64, _f64, _f64, _f64, _int, _int, _int] + [_f64] * 7 + [_dp, _i64, _f64]
-    L.xinv_general_3d_f64.argtypes = [_dp] * 9 + gen3d_scal
-    L.xinv_general_3d_f64_batched.argtypes = [_dp] * 9 + [_i64, _ip] + gen3d_scal + [_opt]
-    L.xinv_general_3d_f64_dev.argtypes = [_vp] * 9 + [_i64, _ip] + gen3d_scal + [_opt, _vp]
-    # 1-D standard form: xc, delx, BCx, delxSqr, optArg, undef, flags, mxLoop, tolerance
-    std1d_scal = [_i64, _f64, _int, _f64, _f64, _f64, _dp, _i64, _f64]
-    L.xinv_standard_1d_f64.argtypes = [_dp] * 4 + std1d_scal + [_opt]
-    L.xinv_standard_1d_f64_batched.argtypes = [_dp] * 4 + [_i64, _ip] + std1d_scal + [_opt]
-    L.xinv_standard_1d_f64_dev.argtypes = [_vp] * 4 + [_i64, _ip] + std1d_scal + [_opt, _vp]
+    # the operator forms: every entry point's argument list comes from the table (xinvert_amd/forms.py)
+    from . import forms
+    for kind, f in forms.FORMS.items():
+        for entry in ('single', 'batched', 'dev') + (('plan',) if f.resident else ()):
+            getattr(L, forms.symbol(kind, entry)).argtypes = forms.argtypes(kind, entry)
     L.xinv_gm_flow_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _f64, _int, _vp]
     L.xinv_abs_norm_f64_dev.argtypes = [_vp, _i64, _f64, _dp, _vp]
     # finite differences: in[], nin, out[], nout, ndim, shape, mode, nterms, iterm, dterm, tab, ntab, mask_axis, mask_off
@@ -145,15 +119,6 @@ def load():
     # prolong(coarse, fine, force, nbatch, ndim, cshape, fshape, idx, w, keep_edges, undef, stream)
     L.xinv_mg_restrict_f64_dev.argtypes = [_vp, _vp, _i64, _int, _ip, _ip, _f64, _vp]
     L.xinv_mg_prolong_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _int, _ip, _ip, _vp, _vp, _int, _f64, _vp]
-    # resident plans: the *_dev argument lists without S / flags / mxLoop / tolerance, behind the handle's address
-    _pp = ctypes.POINTER(_vp)
-    no_tail = lambda scal: scal[:-3]                     # (drop flags, mxLoop, tolerance)
-    L.xinv_plan_create_standard_2d_f64_dev.argtypes = [_pp] + [_vp] * 4 + [_i64, _ip] + no_tail(std2d_scal) + [_opt, _vp]
-    L.xinv_plan_create_general_2d_f64_dev.argtypes = [_pp] + [_vp] * 7 + [_i64, _ip] + no_tail(gen2d_scal) + [_opt, _vp]
-    L.xinv_plan_create_standard_3d_f64_dev.argtypes = [_pp] + [_vp] * 4 + [_i64, _ip] + no_tail(std3d_scal) + [_opt, _vp]
-    L.xinv_plan_create_general_3d_f64_dev.argtypes = [_pp] + [_vp] * 8 + [_i64, _ip] + no_tail(gen3d_scal) + [_opt, _vp]
-    L.xinv_plan_create_general_bih_2d_f64_dev.argtypes = [_pp] + [_vp] * 10 + [_i64, _ip] + no_tail(bih_scal) + [_opt, _vp]
-    L.xinv_plan_create_standard_2d_test_f64_dev.argtypes = [_pp] + [_vp] * 6 + [_i64, _ip] + no_tail(std2d_scal) + [_opt, _vp]
     L.xinv_plan_solve_f64_dev.argtypes = [_vp, _vp, _dp, _i64, _f64, _vp]
     L.xinv_plan_solve_frames_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _dp, _i64, _f64, _vp]
     L.xinv_plan_refresh.argtypes = [_vp, _vp]

@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, forms
 from .field import Field, LazyForcing, aligned, undef_as
 
 # default undefined value (reference core.py:15)
@@ -136,8 +136,7 @@ def _prep_coef(c, F, perm, core_shape, nbatch, allow_null=False):
     return _prep_coef(t, F, perm, core_shape, nbatch, allow_null)
 
 
-_KIND_OF = {'inv_standard2D': 'std2d', 'inv_standard2D_test': 'std2dt', 'inv_general2D': 'gen2d',
-            'inv_general2D_bih': 'bih2d', 'inv_standard3D': 'std3d', 'inv_general3D': 'gen3d'}
+_KIND_OF = {f.inv: k for k, f in forms.FORMS.items() if f.resident}
 
 
 class Resident:
@@ -163,7 +162,7 @@ class Resident:
                                             ).reshape((nbatch,) + core_shape)
         cs, shared = [], []
         for k, c in enumerate(coefs):
-            a, st, rc = _prep_coef(c, F, self.perm, core_shape, nbatch, allow_null=(k == 1 and kind in ('std2d', 'gen2d')))
+            a, st, rc = _prep_coef(c, F, self.perm, core_shape, nbatch, allow_null=(k == 1 and forms.FORMS[kind].null_B))
             if a is None:
                 a = np.zeros(core_shape)                              # ResidentProblem passes it as NULL again
             elif rc:                                                   # one value per row STAYS one value per row: a stride-0 view
@@ -173,22 +172,7 @@ class Resident:
                 shared.append(k)
             cs.append(a)
         cs.append(tr(F.values))
-        ip = iParams
-        p = dict(kind=kind, S0=tr(S.values), coefs=cs, shared=tuple(shared), undef=_undeftmp,
-                 optArg=float(ip['optArg']), delxSqr=float(ip['del1Sqr']))
-        BCs = list(ip['BCs'])
-        if len(dims) == 2:
-            p.update(yc=int(ip['gc2']), xc=int(ip['gc1']), dely=float(ip['del2']), delx=float(ip['del1']),
-                     BCy=BCs[0], BCx=BCs[1], ratio=float(ip['ratio']), ratioQtr=float(ip['ratioQtr']),
-                     ratioSqr=float(ip['ratioSqr']))
-            if kind == 'bih2d':
-                p.update(delxSSr=float(ip['del1SSr']), delxTr=float(ip['del1Tr']), ratioSSr=float(ip['ratioSSr']))
-        else:
-            p.update(zc=int(ip['gc3']), yc=int(ip['gc2']), xc=int(ip['gc1']), delz=float(ip['del3']),
-                     dely=float(ip['del2']), delx=float(ip['del1']), BCz=BCs[0], BCy=BCs[1], BCx=BCs[2],
-                     ratio2Sqr=float(ip['ratio2Sqr']), ratio1Sqr=float(ip['ratio1Sqr']))
-            if kind == 'gen3d':
-                p.update(ratio2=float(ip['ratio2']), ratio1=float(ip['ratio1']))
+        p = dict(forms.from_iparams(kind, iParams, _undeftmp), S0=tr(S.values), coefs=cs, shared=tuple(shared))
         self.iParams = iParams
         dev = int(iParams.get('device', -1))
         if dev < 0:
@@ -393,7 +377,7 @@ def _solve(kind, coefs, F, S, dims, iParams):
     rowconst = 0
     for k, c in enumerate(coefs):
         a, st, rc = _prep_coef(c, F, perm, core_shape, nbatch,
-                               allow_null=(k == 1 and kind in ('std2d', 'gen2d')))
+                               allow_null=(k == 1 and forms.FORMS[kind].null_B))
         if kind == 'std1d':
             if a is not None and a.dtype != np.float64:
                 a = a.astype(np.float64)
@@ -407,7 +391,7 @@ def _solve(kind, coefs, F, S, dims, iParams):
     strides.append(n)
 
     flags = np.tile(np.array([0.0, 1.0, 0.0]), (nbatch, 1))
-    BCs = [_lib.bc(b) for b in iParams['BCs']]
+    scal = forms.scalars(forms.from_iparams(kind, iParams, _undeftmp))
     # float32 arrays travel as float32 with their bit in xinv_options.f32_mask: derived from the dtypes of the arrays
     # actually handed over, and checked against what the code above meant to send (S, the forcing)
     f32_mask = sum(1 << k for k, a_ in enumerate(arrs) if a_ is not None and a_.dtype == np.float32)
@@ -425,51 +409,7 @@ def _solve(kind, coefs, F, S, dims, iParams):
     st = _lib.strides_arg(strides)
     ptrs = [_lib.hptr(a, f32=bool((f32_mask >> k) & 1)) for k, a in enumerate(arrs)]
     mx, tol = int(iParams['mxLoop']), float(iParams['tolerance'])
-    if kind == 'std1d':                                      # (one device: _device_list is not asked)
-        rc = L.xinv_standard_1d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc1'], float(iParams['del1']), BCs[0], float(iParams['del1Sqr']),
-            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
-    elif kind == 'std2d':
-        rc = L.xinv_standard_2d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc2'], iParams['gc1'],
-            float(iParams['del2']), float(iParams['del1']), BCs[0], BCs[1],
-            float(iParams['del1Sqr']), float(iParams['ratioQtr']), float(iParams['ratioSqr']),
-            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
-    elif kind == 'gen2d':
-        rc = L.xinv_general_2d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc2'], iParams['gc1'],
-            float(iParams['del2']), float(iParams['del1']), BCs[0], BCs[1],
-            float(iParams['del1Sqr']), float(iParams['ratio']), float(iParams['ratioQtr']),
-            float(iParams['ratioSqr']), float(iParams['optArg']), _undeftmp,
-            _lib.hptr(flags), mx, tol, opt)
-    elif kind == 'std2dt':
-        rc = L.xinv_standard_2d_test_f64_batched(
-            *ptrs, nbatch, st, iParams['gc2'], iParams['gc1'],
-            float(iParams['del2']), float(iParams['del1']), BCs[0], BCs[1],
-            float(iParams['del1Sqr']), float(iParams['ratioQtr']), float(iParams['ratioSqr']),
-            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
-    elif kind == 'bih2d':
-        rc = L.xinv_general_bih_2d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc2'], iParams['gc1'],
-            float(iParams['del2']), float(iParams['del1']), BCs[0], BCs[1],
-            float(iParams['del1SSr']), float(iParams['del1Tr']), float(iParams['del1Sqr']),
-            float(iParams['ratio']), float(iParams['ratioSSr']), float(iParams['ratioQtr']),
-            float(iParams['ratioSqr']), float(iParams['optArg']), _undeftmp,
-            _lib.hptr(flags), mx, tol, opt)
-    elif kind == 'gen3d':
-        rc = L.xinv_general_3d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc3'], iParams['gc2'], iParams['gc1'],
-            float(iParams['del3']), float(iParams['del2']), float(iParams['del1']),
-            BCs[0], BCs[1], BCs[2], float(iParams['del1Sqr']), float(iParams['ratio2']),
-            float(iParams['ratio1']), float(iParams['ratio2Sqr']), float(iParams['ratio1Sqr']),
-            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
-    else:
-        rc = L.xinv_standard_3d_f64_batched(
-            *ptrs, nbatch, st, iParams['gc3'], iParams['gc2'], iParams['gc1'],
-            float(iParams['del3']), float(iParams['del2']), float(iParams['del1']),
-            BCs[0], BCs[1], BCs[2], float(iParams['del1Sqr']),
-            float(iParams['ratio2Sqr']), float(iParams['ratio1Sqr']),
-            float(iParams['optArg']), _undeftmp, _lib.hptr(flags), mx, tol, opt)
+    rc = getattr(L, forms.symbol(kind, 'batched'))(*ptrs, nbatch, st, *scal, _lib.hptr(flags), mx, tol, opt)
     _lib.check(rc)
 
     # in place on S, as the reference (S.loc[sel].values are views of initS, apps.py:2159)

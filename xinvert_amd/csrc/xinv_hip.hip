@@ -73,137 +73,6 @@ static inline void xinv_cpu_relax()
 #include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
 #include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
 
-// ------------------------------------------------------------------ problem builders
-static void set_scal2d(Problem &p, double delx, double delxSqr, double ratio, double ratioQtr,
-                       double ratioSqr, double optArg, double undef)
-{
-    memset(&p.sc_, 0, sizeof p.sc_);
-    p.sc_.delx = delx; p.sc_.delxSqr = delxSqr; p.sc_.ratio = ratio;
-    p.sc_.ratioQtr = ratioQtr; p.sc_.ratioSqr = ratioSqr; p.sc_.optArg = optArg;
-    p.sc_.undef = undef;
-}
-
-static Problem mk_std2d(double *S, const double *A, const double *B, const double *C,
-                        const double *F, int64_t nbatch, const int64_t *st, int64_t yc,
-                        int64_t xc, double delx, int BCy, int BCx, double delxSqr,
-                        double ratioQtr, double ratioSqr, double optArg, double undef,
-                        int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_STD2D; p.nbatch = nbatch; p.zc = 1; p.yc = yc; p.xc = xc;
-    p.S = S; p.c[0] = A; p.c[1] = B; p.c[2] = C; p.c[3] = F; p.ncoef = 4;
-    const int64_t n = yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 4; q++) p.sc[q] = st ? st[1 + q] : n;
-    p.BCz = 0; p.BCy = BCy; p.BCx = BCx;
-    set_scal2d(p, delx, delxSqr, 0.0, ratioQtr, ratioSqr, optArg, undef);
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 1;
-    return p;
-}
-
-static Problem mk_gen2d(double *S, const double *A, const double *B, const double *C,
-                        const double *D, const double *E, const double *F, const double *G,
-                        int64_t nbatch, const int64_t *st, int64_t yc, int64_t xc, double delx,
-                        int BCy, int BCx, double delxSqr, double ratio, double ratioQtr,
-                        double ratioSqr, double optArg, double undef, int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_GEN2D; p.nbatch = nbatch; p.zc = 1; p.yc = yc; p.xc = xc;
-    p.S = S;
-    p.c[0] = A; p.c[1] = B; p.c[2] = C; p.c[3] = D; p.c[4] = E; p.c[5] = F; p.c[6] = G;
-    p.ncoef = 7;
-    const int64_t n = yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 7; q++) p.sc[q] = st ? st[1 + q] : n;
-    p.BCz = 0; p.BCy = BCy; p.BCx = BCx;
-    set_scal2d(p, delx, delxSqr, ratio, ratioQtr, ratioSqr, optArg, undef);
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 0;
-    return p;
-}
-
-static Problem mk_std2dt(double *S, const double *const *co, int64_t nbatch, const int64_t *st,
-                         int64_t yc, int64_t xc, double delx, int BCy, int BCx, double delxSqr,
-                         double ratioQtr, double ratioSqr, double optArg, double undef,
-                         int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_STD2DT; p.nbatch = nbatch; p.zc = 1; p.yc = yc; p.xc = xc;
-    p.S = S; p.ncoef = 6;
-    const int64_t n = yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 6; q++) { p.c[q] = co[q]; p.sc[q] = st ? st[1 + q] : n; }
-    p.BCz = 0; p.BCy = BCy; p.BCx = BCx;
-    set_scal2d(p, delx, delxSqr, 0.0, ratioQtr, ratioSqr, optArg, undef);
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 1;
-    return p;
-}
-
-static Problem mk_bih2d(double *S, const double *const *co, int64_t nbatch, const int64_t *st,
-                        int64_t yc, int64_t xc, int BCy, int BCx, double delxSSr, double delxTr,
-                        double delxSqr, double ratio, double ratioSSr, double ratioQtr,
-                        double ratioSqr, double optArg, double undef, int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_BIH2D; p.nbatch = nbatch; p.zc = 1; p.yc = yc; p.xc = xc;
-    p.S = S; p.ncoef = 10;
-    const int64_t n = yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 10; q++) { p.c[q] = co[q]; p.sc[q] = st ? st[1 + q] : n; }
-    p.BCz = 0; p.BCy = BCy; p.BCx = BCx;
-    memset(&p.sc_, 0, sizeof p.sc_);
-    p.sc_.delxSSr = delxSSr; p.sc_.delxTr = delxTr; p.sc_.delxSqr = delxSqr; p.sc_.ratio = ratio;
-    p.sc_.ratioSSr = ratioSSr; p.sc_.ratioQtr = ratioQtr; p.sc_.ratioSqr = ratioSqr;
-    p.sc_.optArg = optArg; p.sc_.undef = undef;
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 0;
-    return p;
-}
-
-static Problem mk_std3d(double *S, const double *A, const double *B, const double *C,
-                        const double *F, int64_t nbatch, const int64_t *st, int64_t zc,
-                        int64_t yc, int64_t xc, int BCz, int BCy, int BCx, double delxSqr,
-                        double ratio2Sqr, double ratio1Sqr, double optArg, double undef,
-                        int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_STD3D; p.nbatch = nbatch; p.zc = zc; p.yc = yc; p.xc = xc;
-    p.S = S; p.c[0] = A; p.c[1] = B; p.c[2] = C; p.c[3] = F; p.ncoef = 4;
-    const int64_t n = zc * yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 4; q++) p.sc[q] = st ? st[1 + q] : n;
-    p.BCz = BCz; p.BCy = BCy; p.BCx = BCx;
-    memset(&p.sc_, 0, sizeof p.sc_);
-    p.sc_.delxSqr = delxSqr; p.sc_.ratio2Sqr = ratio2Sqr; p.sc_.ratio1Sqr = ratio1Sqr;
-    p.sc_.optArg = optArg; p.sc_.undef = undef;
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 0;
-    return p;
-}
-
-static Problem mk_gen3d(double *S, const double *const *c, int64_t nbatch, const int64_t *st,
-                        int64_t zc, int64_t yc, int64_t xc, double delx, int BCz, int BCy, int BCx,
-                        double delxSqr, double ratio2, double ratio1, double ratio2Sqr,
-                        double ratio1Sqr, double optArg, double undef, int64_t mxLoop, double tol)
-{
-    Problem p;
-    memset(&p, 0, sizeof p);
-    p.kind = KIND_GEN3D; p.nbatch = nbatch; p.zc = zc; p.yc = yc; p.xc = xc;
-    p.S = S; p.ncoef = 8;
-    const int64_t n = zc * yc * xc;
-    p.sS = st ? st[0] : n;
-    for (int q = 0; q < 8; q++) { p.c[q] = c[q]; p.sc[q] = st ? st[1 + q] : n; }
-    p.BCz = BCz; p.BCy = BCy; p.BCx = BCx;
-    memset(&p.sc_, 0, sizeof p.sc_);
-    p.sc_.delx = delx; p.sc_.delxSqr = delxSqr; p.sc_.ratio2 = ratio2; p.sc_.ratio1 = ratio1;
-    p.sc_.ratio2Sqr = ratio2Sqr; p.sc_.ratio1Sqr = ratio1Sqr;
-    p.sc_.optArg = optArg; p.sc_.undef = undef;
-    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = 0;
-    return p;
-}
-
 // ------------------------------------------------------------------ C-ABI
 extern "C" {
 
@@ -240,6 +109,39 @@ void xinv_abi_sizes(int32_t *options_bytes, int32_t *stats_bytes)
 
 #define GUARD(expr) try { return (expr); } catch (const std::exception &e) { t_err = e.what(); return XINV_ERR_HIP; } catch (...) { t_err = "unknown C++ exception"; return XINV_ERR_HIP; }
 
+// ---- the operator forms: one problem builder, one way through an entry point ---------------------------------------
+// `c`: the FORM[kind].ncoef coefficient arrays, the forcing last; `st`: batch strides of S and of every array (NULL: one
+// slice); the 2-D forms pass zc = 1 and BCz = 0; `sc`: the fields of XinvScal the form's kernels read, the rest 0.
+static Problem mk_problem(int kind, double *S, const double *const *c, int64_t nbatch, const int64_t *st, int64_t zc,
+                          int64_t yc, int64_t xc, int BCz, int BCy, int BCx, const XinvScal &sc, int64_t mxLoop, double tol)
+{
+    Problem p;
+    memset(&p, 0, sizeof p);
+    p.kind = kind; p.nbatch = nbatch; p.zc = zc; p.yc = yc; p.xc = xc;
+    p.S = S; p.ncoef = FORM[kind].ncoef;
+    const int64_t n = zc * yc * xc;
+    p.sS = st ? st[0] : n;
+    for (int q = 0; q < p.ncoef; q++) { p.c[q] = c[q]; p.sc[q] = st ? st[1 + q] : n; }
+    p.BCz = BCz; p.BCy = BCy; p.BCx = BCx;
+    p.sc_ = sc;
+    p.stop.mxLoop = mxLoop; p.stop.tolerance = tol; p.stop.stop_on_zero_norm = FORM[kind].stop_on_zero_norm;
+    return p;
+}
+
+// What every entry point of a form does with its arguments.  RUN_SINGLE: one slice, no strides, default options;
+// RUN_PLAN: `plan` instead of S, flags, mxLoop and tolerance (the callers pass nullptr, nullptr, 0, 0.0).
+enum { RUN_SINGLE, RUN_BATCHED, RUN_DEV, RUN_PLAN };
+static int run_form(int how, int kind, xinv_plan **plan, double *S, const double *const *c, int64_t nbatch,
+                    const int64_t *strides, int64_t zc, int64_t yc, int64_t xc, int BCz, int BCy, int BCx,
+                    const XinvScal &sc, double *flags, int64_t mxLoop, double tolerance, const xinv_options *opt,
+                    void *stream)
+{
+    if (how != RUN_SINGLE && !strides) return fail_arg("null strides");
+    Problem p = mk_problem(kind, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, mxLoop, tolerance);
+    GUARD(how == RUN_PLAN ? plan_create(plan, p, opt, (hipStream_t)stream)
+          : how == RUN_DEV ? solve_dev(p, flags, opt, (hipStream_t)stream) : solve_host(p, flags, opt))
+}
+
 int xinv_standard_2d_f64(double *S, const double *A, const double *B, const double *C,
                          const double *F, int64_t yc, int64_t xc, double dely, double delx,
                          int BCy, int BCx, double delxSqr, double ratioQtr, double ratioSqr,
@@ -247,9 +149,12 @@ int xinv_standard_2d_f64(double *S, const double *A, const double *B, const doub
                          double tolerance)
 {
     (void)dely;
-    Problem p = mk_std2d(S, A, B, C, F, 1, nullptr, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr,
-                         ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_STD2D, nullptr, S, c, 1, nullptr, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_general_2d_f64(double *S, const double *A, const double *B, const double *C,
@@ -260,9 +165,12 @@ int xinv_general_2d_f64(double *S, const double *A, const double *B, const doubl
                         double tolerance)
 {
     (void)dely;
-    Problem p = mk_gen2d(S, A, B, C, D, E, F, G, 1, nullptr, yc, xc, delx, BCy, BCx, delxSqr,
-                         ratio, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr;
+    sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_GEN2D, nullptr, S, c, 1, nullptr, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_standard_3d_f64(double *S, const double *A, const double *B, const double *C,
@@ -272,9 +180,11 @@ int xinv_standard_3d_f64(double *S, const double *A, const double *B, const doub
                          double *flags, int64_t mxLoop, double tolerance)
 {
     (void)delz; (void)dely; (void)delx;
-    Problem p = mk_std3d(S, A, B, C, F, 1, nullptr, zc, yc, xc, BCz, BCy, BCx, delxSqr,
-                         ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_STD3D, nullptr, S, c, 1, nullptr, zc, yc, xc, BCz, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_standard_2d_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -285,10 +195,12 @@ int xinv_standard_2d_f64_batched(double *S, const double *A, const double *B, co
                                  double tolerance, const xinv_options *opt)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std2d(S, A, B, C, F, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr,
-                         ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_STD2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_general_2d_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -300,10 +212,12 @@ int xinv_general_2d_f64_batched(double *S, const double *A, const double *B, con
                                 int64_t mxLoop, double tolerance, const xinv_options *opt)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_gen2d(S, A, B, C, D, E, F, G, nbatch, strides, yc, xc, delx, BCy, BCx,
-                         delxSqr, ratio, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr;
+    sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_GEN2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_standard_3d_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -315,10 +229,11 @@ int xinv_standard_3d_f64_batched(double *S, const double *A, const double *B, co
                                  const xinv_options *opt)
 {
     (void)delz; (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std3d(S, A, B, C, F, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, delxSqr,
-                         ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_STD3D, nullptr, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_standard_2d_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -329,10 +244,12 @@ int xinv_standard_2d_f64_dev(double *S, const double *A, const double *B, const 
                              double tolerance, const xinv_options *opt, void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std2d(S, A, B, C, F, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr,
-                         ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_DEV, KIND_STD2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, opt, stream);
 }
 
 int xinv_general_2d_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -344,10 +261,12 @@ int xinv_general_2d_f64_dev(double *S, const double *A, const double *B, const d
                             const xinv_options *opt, void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_gen2d(S, A, B, C, D, E, F, G, nbatch, strides, yc, xc, delx, BCy, BCx,
-                         delxSqr, ratio, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr;
+    sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_DEV, KIND_GEN2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, opt, stream);
 }
 
 int xinv_standard_3d_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -359,10 +278,11 @@ int xinv_standard_3d_f64_dev(double *S, const double *A, const double *B, const 
                              const xinv_options *opt, void *stream)
 {
     (void)delz; (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std3d(S, A, B, C, F, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, delxSqr,
-                         ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_DEV, KIND_STD3D, nullptr, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, stream);
 }
 
 int xinv_general_3d_f64(double *S, const double *A, const double *B, const double *C,
@@ -374,10 +294,12 @@ int xinv_general_3d_f64(double *S, const double *A, const double *B, const doubl
                         double tolerance)
 {
     (void)delz; (void)dely;
-    const double *c[8] = { A, B, C, D, E, F, G, H };
-    Problem p = mk_gen3d(S, c, 1, nullptr, zc, yc, xc, delx, BCz, BCy, BCx, delxSqr, ratio2, ratio1,
-                         ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr;
+    sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_GEN3D, nullptr, S, c, 1, nullptr, zc, yc, xc, BCz, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_general_3d_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -390,11 +312,12 @@ int xinv_general_3d_f64_batched(double *S, const double *A, const double *B, con
                                 int64_t mxLoop, double tolerance, const xinv_options *opt)
 {
     (void)delz; (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *c[8] = { A, B, C, D, E, F, G, H };
-    Problem p = mk_gen3d(S, c, nbatch, strides, zc, yc, xc, delx, BCz, BCy, BCx, delxSqr, ratio2,
-                         ratio1, ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr;
+    sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_GEN3D, nullptr, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_general_3d_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -407,11 +330,12 @@ int xinv_general_3d_f64_dev(double *S, const double *A, const double *B, const d
                             const xinv_options *opt, void *stream)
 {
     (void)delz; (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *c[8] = { A, B, C, D, E, F, G, H };
-    Problem p = mk_gen3d(S, c, nbatch, strides, zc, yc, xc, delx, BCz, BCy, BCx, delxSqr, ratio2,
-                         ratio1, ratio2Sqr, ratio1Sqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr;
+    sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_DEV, KIND_GEN3D, nullptr, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, stream);
 }
 
 int xinv_general_bih_2d_f64(double *S, const double *A, const double *B, const double *C,
@@ -423,10 +347,12 @@ int xinv_general_bih_2d_f64(double *S, const double *A, const double *B, const d
                             double undef, double *flags, int64_t mxLoop, double tolerance)
 {
     (void)dely; (void)delx;
-    const double *co[10] = { A, B, C, D, E, F, G, H, I, J };
-    Problem p = mk_bih2d(S, co, 1, nullptr, yc, xc, BCy, BCx, delxSSr, delxTr, delxSqr, ratio,
-                         ratioSSr, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, D, E, F, G, H, I, J };
+    XinvScal sc = {};
+    sc.delxSSr = delxSSr; sc.delxTr = delxTr; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioSSr = ratioSSr;
+    sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_BIH2D, nullptr, S, c, 1, nullptr, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_general_bih_2d_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -440,11 +366,12 @@ int xinv_general_bih_2d_f64_batched(double *S, const double *A, const double *B,
                                     int64_t mxLoop, double tolerance, const xinv_options *opt)
 {
     (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    const double *co[10] = { A, B, C, D, E, F, G, H, I, J };
-    Problem p = mk_bih2d(S, co, nbatch, strides, yc, xc, BCy, BCx, delxSSr, delxTr, delxSqr,
-                         ratio, ratioSSr, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, D, E, F, G, H, I, J };
+    XinvScal sc = {};
+    sc.delxSSr = delxSSr; sc.delxTr = delxTr; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioSSr = ratioSSr;
+    sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_BIH2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_general_bih_2d_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -458,11 +385,12 @@ int xinv_general_bih_2d_f64_dev(double *S, const double *A, const double *B, con
                                 double tolerance, const xinv_options *opt, void *stream)
 {
     (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    const double *co[10] = { A, B, C, D, E, F, G, H, I, J };
-    Problem p = mk_bih2d(S, co, nbatch, strides, yc, xc, BCy, BCx, delxSSr, delxTr, delxSqr,
-                         ratio, ratioSSr, ratioQtr, ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G, H, I, J };
+    XinvScal sc = {};
+    sc.delxSSr = delxSSr; sc.delxTr = delxTr; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioSSr = ratioSSr;
+    sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_DEV, KIND_BIH2D, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, opt, stream);
 }
 
 int xinv_standard_2d_test_f64(double *S, const double *A, const double *B, const double *C,
@@ -472,10 +400,12 @@ int xinv_standard_2d_test_f64(double *S, const double *A, const double *B, const
                               double undef, double *flags, int64_t mxLoop, double tolerance)
 {
     (void)dely;
-    const double *co[6] = { A, B, C, D, E, F };
-    Problem p = mk_std2dt(S, co, 1, nullptr, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr, ratioSqr,
-                          optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, nullptr))
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_SINGLE, KIND_STD2DT, nullptr, S, c, 1, nullptr, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, nullptr, nullptr);
 }
 
 int xinv_standard_2d_test_f64_batched(double *S, const double *A, const double *B, const double *C,
@@ -487,11 +417,12 @@ int xinv_standard_2d_test_f64_batched(double *S, const double *A, const double *
                                       double tolerance, const xinv_options *opt)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *co[6] = { A, B, C, D, E, F };
-    Problem p = mk_std2dt(S, co, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr,
-                          ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_host(p, flags, opt))
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_BATCHED, KIND_STD2DT, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags,
+                    mxLoop, tolerance, opt, nullptr);
 }
 
 int xinv_standard_2d_test_f64_dev(double *S, const double *A, const double *B, const double *C,
@@ -503,11 +434,12 @@ int xinv_standard_2d_test_f64_dev(double *S, const double *A, const double *B, c
                                   const xinv_options *opt, void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *co[6] = { A, B, C, D, E, F };
-    Problem p = mk_std2dt(S, co, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr,
-                          ratioSqr, optArg, undef, mxLoop, tolerance);
-    GUARD(solve_dev(p, flags, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_DEV, KIND_STD2DT, nullptr, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, flags, mxLoop,
+                    tolerance, opt, stream);
 }
 
 // ---- standard 1-D form (k_std1d) --------------------------------------------------------------------------------
@@ -591,10 +523,12 @@ int xinv_plan_create_standard_2d_f64_dev(xinv_plan **plan, const double *A, cons
                                          const xinv_options *opt, void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std2d(nullptr, A, B, C, F, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr,
-                         ratioSqr, optArg, undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_STD2D, plan, nullptr, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, nullptr, 0,
+                    0.0, opt, stream);
 }
 
 int xinv_plan_create_general_2d_f64_dev(xinv_plan **plan, const double *A, const double *B, const double *C,
@@ -605,10 +539,12 @@ int xinv_plan_create_general_2d_f64_dev(xinv_plan **plan, const double *A, const
                                         void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_gen2d(nullptr, A, B, C, D, E, F, G, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratio,
-                         ratioQtr, ratioSqr, optArg, undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr;
+    sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_GEN2D, plan, nullptr, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, nullptr, 0,
+                    0.0, opt, stream);
 }
 
 int xinv_plan_create_standard_3d_f64_dev(xinv_plan **plan, const double *A, const double *B, const double *C,
@@ -618,10 +554,11 @@ int xinv_plan_create_standard_3d_f64_dev(xinv_plan **plan, const double *A, cons
                                          double optArg, double undef, const xinv_options *opt, void *stream)
 {
     (void)delz; (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    Problem p = mk_std3d(nullptr, A, B, C, F, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, delxSqr, ratio2Sqr,
-                         ratio1Sqr, optArg, undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_STD3D, plan, nullptr, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, nullptr,
+                    0, 0.0, opt, stream);
 }
 
 int xinv_plan_create_general_3d_f64_dev(xinv_plan **plan, const double *A, const double *B, const double *C,
@@ -633,11 +570,12 @@ int xinv_plan_create_general_3d_f64_dev(xinv_plan **plan, const double *A, const
                                         const xinv_options *opt, void *stream)
 {
     (void)delz; (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *c[8] = { A, B, C, D, E, F, G, H };
-    Problem p = mk_gen3d(nullptr, c, nbatch, strides, zc, yc, xc, delx, BCz, BCy, BCx, delxSqr, ratio2, ratio1,
-                         ratio2Sqr, ratio1Sqr, optArg, undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr;
+    sc.ratio1Sqr = ratio1Sqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_GEN3D, plan, nullptr, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, nullptr,
+                    0, 0.0, opt, stream);
 }
 
 int xinv_plan_create_general_bih_2d_f64_dev(xinv_plan **plan, const double *A, const double *B, const double *C,
@@ -649,11 +587,12 @@ int xinv_plan_create_general_bih_2d_f64_dev(xinv_plan **plan, const double *A, c
                                             double optArg, double undef, const xinv_options *opt, void *stream)
 {
     (void)dely; (void)delx;
-    if (!strides) return fail_arg("null strides");
-    const double *co[10] = { A, B, C, D, E, F, G, H, I, J };
-    Problem p = mk_bih2d(nullptr, co, nbatch, strides, yc, xc, BCy, BCx, delxSSr, delxTr, delxSqr, ratio, ratioSSr,
-                         ratioQtr, ratioSqr, optArg, undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F, G, H, I, J };
+    XinvScal sc = {};
+    sc.delxSSr = delxSSr; sc.delxTr = delxTr; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioSSr = ratioSSr;
+    sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg; sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_BIH2D, plan, nullptr, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, nullptr, 0,
+                    0.0, opt, stream);
 }
 
 int xinv_plan_create_standard_2d_test_f64_dev(xinv_plan **plan, const double *A, const double *B, const double *C,
@@ -664,11 +603,12 @@ int xinv_plan_create_standard_2d_test_f64_dev(xinv_plan **plan, const double *A,
                                               void *stream)
 {
     (void)dely;
-    if (!strides) return fail_arg("null strides");
-    const double *co[6] = { A, B, C, D, E, F };
-    Problem p = mk_std2dt(nullptr, co, nbatch, strides, yc, xc, delx, BCy, BCx, delxSqr, ratioQtr, ratioSqr, optArg,
-                          undef, 0, 0.0);
-    GUARD(plan_create(plan, p, opt, (hipStream_t)stream))
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.optArg = optArg;
+    sc.undef = undef;
+    return run_form(RUN_PLAN, KIND_STD2DT, plan, nullptr, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc, nullptr, 0,
+                    0.0, opt, stream);
 }
 
 int xinv_plan_solve_f64_dev(xinv_plan *plan, double *S, double *flags, int64_t mxLoop, double tolerance, void *stream)

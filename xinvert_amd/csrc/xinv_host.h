@@ -336,13 +336,25 @@ static int ensure_dev(T **p, size_t *cap, size_t need_bytes)
 
 // ------------------------------------------------------------------ problem description
 enum { KIND_STD2D = 0, KIND_GEN2D = 1, KIND_STD3D = 2, KIND_BIH2D = 3, KIND_STD2DT = 4, KIND_GEN3D = 5 };
-static inline bool is3d(int kind) { return kind == KIND_STD3D || kind == KIND_GEN3D; }
+// What the C-ABI's problem builder and validate() need to know about a form, indexed by kind: its coefficient arrays
+// (forcing last), its core rank, whether array 1 (B) may be NULL (identically 0), and the reference's norm == 0 stop
+// (numbas.py:410: the standard 2-D forms only).
+struct FormInfo { int ncoef, rank, null_B, stop_on_zero_norm; };
+static const FormInfo FORM[6] = {
+    /* KIND_STD2D  */ { 4, 2, 1, 1 },       // A,B,C,F
+    /* KIND_GEN2D  */ { 7, 2, 1, 0 },       // A..G
+    /* KIND_STD3D  */ { 4, 3, 0, 0 },       // A,B,C,F
+    /* KIND_BIH2D  */ { 10, 2, 0, 0 },      // A..J
+    /* KIND_STD2DT */ { 6, 2, 0, 1 },       // A..F
+    /* KIND_GEN3D  */ { 8, 3, 0, 0 },       // A..H
+};
+static inline bool is3d(int kind) { return FORM[kind].rank == 3; }
 
 struct Problem {
     int kind;
     int64_t nbatch, zc, yc, xc;
     double *S;
-    const double *c[10];         // std2d/std3d: A,B,C,F ; gen2d: A..G ; bih2d: A..J ; std2dt: A..F ; gen3d: A..H
+    const double *c[10];         // FORM[kind].ncoef arrays, the forcing last
     int64_t sS, sc[10];
     int ncoef;
     unsigned rowconst;           // host entries: arrays given as one value per row (see xinv.h)
@@ -360,7 +372,7 @@ static int validate(const Problem &p, const double *flags)
 {
     if (!p.S || !flags) return fail_arg("null S or flags");
     for (int q = 0; q < p.ncoef; q++)
-        if (!p.c[q] && !(q == 1 && (p.kind == KIND_STD2D || p.kind == KIND_GEN2D)))   // B may be NULL: identically 0
+        if (!p.c[q] && !(q == 1 && FORM[p.kind].null_B))   // B may be NULL: identically 0
             return fail_arg("null coefficient array");
     if (p.nbatch < 1) return fail_arg("nbatch < 1");
     if (p.yc < 3 || p.xc < 3 || (is3d(p.kind) && p.zc < 3))

@@ -14,37 +14,12 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, forms
 
-FN = {'std2d': 'xinv_standard_2d_f64', 'gen2d': 'xinv_general_2d_f64', 'std3d': 'xinv_standard_3d_f64',
-      'bih2d': 'xinv_general_bih_2d_f64', 'std2dt': 'xinv_standard_2d_test_f64',
-      'gen3d': 'xinv_general_3d_f64'}
-
-
-def scalars(p):
-    """Positional scalar arguments between the arrays and `flags` (reference numbas.py:215-219,
-    987-991, 15-19, 745-750, 1204-1209, 420-424)."""
-    b = _lib.bc
-    k = p['kind']
-    if k in ('std2d', 'std2dt'):
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSqr'],
-                p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef']]
-    if k == 'gen2d':
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSqr'],
-                p['ratio'], p['ratioQtr'], p['ratioSqr'], p['optArg'], p['undef']]
-    if k == 'bih2d':
-        return [p['yc'], p['xc'], p['dely'], p['delx'], b(p['BCy']), b(p['BCx']), p['delxSSr'],
-                p['delxTr'], p['delxSqr'], p['ratio'], p['ratioSSr'], p['ratioQtr'], p['ratioSqr'],
-                p['optArg'], p['undef']]
-    if k == 'gen3d':
-        return [p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'], b(p['BCz']), b(p['BCy']),
-                b(p['BCx']), p['delxSqr'], p['ratio2'], p['ratio1'], p['ratio2Sqr'], p['ratio1Sqr'],
-                p['optArg'], p['undef']]
-    return [p['zc'], p['yc'], p['xc'], p['delz'], p['dely'], p['delx'], b(p['BCz']), b(p['BCy']),
-            b(p['BCx']), p['delxSqr'], p['ratio2Sqr'], p['ratio1Sqr'], p['optArg'], p['undef']]
-
-
-PLAN_FN = {k: v.replace('xinv_', 'xinv_plan_create_') + '_dev' for k, v in FN.items()}
+# the forms a batch can be resident for (xinvert_amd/forms.py): C symbol stems, plan constructors, positional scalars
+FN = {k: forms.symbol(k, 'single') for k, f in forms.FORMS.items() if f.resident}
+PLAN_FN = {k: forms.symbol(k, 'plan') for k in FN}
+scalars = forms.scalars
 
 
 class ResidentProblem:
@@ -70,7 +45,8 @@ class ResidentProblem:
         self.use_plan = bool(plan)
         self._plans = {}
         S0 = np.asarray(p['S0'])
-        core_nd = 3 if self.kind in ('std3d', 'gen3d') else 2
+        form = forms.FORMS[self.kind]
+        core_nd = form.rank
         if S0.ndim == core_nd:
             S0 = S0[None]
         lo, hi = members if members is not None else (0, S0.shape[0])
@@ -96,7 +72,7 @@ class ResidentProblem:
             if is_shared:
                 # the cross coefficient B of the 2-D standard / general forms travels as NULL when it
                 # is identically zero, exactly as the front end hands it over (core._prep_coef)
-                if null_zero_B and k == 1 and self.kind in ('std2d', 'gen2d') and not c.any():
+                if null_zero_B and k == 1 and form.null_B and not c.any():
                     self.coefs.append(None)
                 elif rc:
                     self.coefs.append(up(c[..., 0])); self.rowconst |= 1 << k
