@@ -50,6 +50,8 @@ extern "C" {
 /* (3 was XINV_PATH_SMALL, a register-resident solver for small slices: removed in version 400, it
    never beat the streaming kernels on the shapes it was built for -- DESIGN.md 4.7) */
 #define XINV_PATH_WAVE1D 4   /* stats only: the 1-D form's register-resident kernel (k_std1d), whatever path was asked */
+#define XINV_PATH_DIRECT1D 5 /* the 1-D form only, on request: one tridiagonal solve per member (k_tridiag) instead of
+                                sweeps -- the fixed point the sweeps converge to; XINV_ERR_ARG for every other form */
 
 #define XINV_FLAG_NO_XUNIFORM 1  /* stream every coefficient array in full: do not look for rows
                                     that are constant along x                                    */
@@ -384,7 +386,18 @@ int xinv_standard_2d_test_f64_dev(double *S, const double *A, const double *B, c
  * Options: sweeps_per_launch = the per-launch sweep budget (0 = 2048; the result does not depend on it), check_every =
  * launches between two polls of the control blocks (0 = 4); timing = 1 fills sweep_ms.
  * XINV_ERR_ARG for: xc < 3; xc > 8192 (16 wavefronts x 64 lanes x 8 points); ndev > 1 or -1 (one device only);
- * f32_mask != 0 (float64 only); prep_flags != 0 (no front-end passes); XINV_FLAG_FMA.  xinv_stats.path = XINV_PATH_WAVE1D. */
+ * f32_mask != 0 (float64 only); prep_flags != 0 (no front-end passes); XINV_FLAG_FMA.  xinv_stats.path = XINV_PATH_WAVE1D.
+ *
+ * opt->path = XINV_PATH_DIRECT1D: the equation is linear and tridiagonal, and the three entries solve it directly -- the
+ * fixed point of the sweeps above, by the reference's own trace / traceCyclic recurrence (below), the system assembled
+ * from S, A, B, F inside the kernel.  Rows default to x[i] = S[i] (the first guess); live rows (1 .. xc-2, and 0 and xc-1
+ * when periodic, where F[i], A[i], A[i+1], B[i] != undef): lower A[i] / delxSqr, upper A[i+1] / delxSqr, diagonal
+ * B[i] - (A[i+1] + A[i]) / delxSqr, right-hand side F[i].  'extend': x[0] - x[1] = 0 when S[1] != undef, x[xc-1] - x[xc-2]
+ * = 0 when S[xc-2] != undef.  'periodic': traceCyclic where both end rows are live; where one is an identity row its
+ * value is known, and the other end's wrap term times it moves to the right-hand side of a plain trace.  optArg, mxLoop,
+ * tolerance, sweeps_per_launch and check_every are ignored, xc may exceed 8192, flags = [overflow, 0, 0] with overflow =
+ * 1 where the result holds a non-finite value (a NaN coefficient, a singular system: S is left as computed), and
+ * xinv_stats.path = XINV_PATH_DIRECT1D. */
 int xinv_standard_1d_f64(double *S, const double *A, const double *B, const double *F, int64_t xc, double delx,
                          int BCx, double delxSqr, double optArg, double undef, double *flags, int64_t mxLoop,
                          double tolerance, const xinv_options *opt);
@@ -398,6 +411,26 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
                              const int64_t *strides, int64_t xc, double delx, int BCx, double delxSqr,
                              double optArg, double undef, double *flags, int64_t mxLoop, double tolerance,
                              const xinv_options *opt, void *stream);
+
+/* ---- tridiagonal systems: numbas.trace / numbas.traceCyclic (numbas.py:1589-1685) -------------------------------------
+ * nbatch systems of n unknowns, a[i-1] x[i-1] + b[i] x[i] + c[i] x[i+1] = d[i]: a, c hold n-1 values per system, b, d, x n,
+ * a0 and cn (the corners of the periodic system: row 0's lower, row n-1's upper) one.  Both NULL: trace; both non-NULL:
+ * traceCyclic.  strides[]: x, a, b, c, d (and a0, cn when given) in elements between two systems; 0 = one copy shared by
+ * every system (not x).  One system per lane runs the reference's recurrence -- same expressions, association and loop
+ * order, no contraction: the reference's bits --, the systems moving between HBM and LDS in coalesced chunks (kernel
+ * k_tridiag, xinv_tridiag.h).  xinv_tridiag_f64 takes host pointers (upload, one solve, download), xinv_tridiag_f64_dev
+ * device pointers and queues on `stream`: it returns before the solve has run.  The forward pass keeps its intermediate
+ * arrays in one buffer per device, which the library owns (no allocation in steady state; the buffer grows when a larger
+ * call comes); an event behind every queued solve orders the next user of that buffer after it, so calls from several
+ * streams or threads are safe, and run one after another on a device.  (Not for stream capture: the buffer may grow.)
+ * The host-pointer entry is the plain one, like xinv_standard_1d_f64: it allocates and frees one device block per call
+ * and copies from pageable memory on the null stream.  XINV_ERR_ARG for n < 2, nbatch < 1, a null array, exactly one of
+ * a0 / cn NULL, or a stride shorter than one system.
+ *   xinv_tridiag_f64(x, a, b, c, d, a0, cn, nbatch, strides, n)
+ *   xinv_tridiag_f64_dev(x, a, b, c, d, a0, cn, nbatch, strides, n, stream)
+ * They are no operator form -- no S, flags, options or stop rule --, so their prototypes live in a header of their own,
+ * which this one includes: a caller of xinv.h has them. */
+#include "xinv_trace.h"
 
 /* ---- resident plans: what a solve derives from the coefficient stack, built once -------------------------------
  * The reference calls its kernel again and again on ONE coefficient stack: apps.animate_iteration (apps.py:1031-1044:

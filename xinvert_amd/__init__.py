@@ -11,6 +11,7 @@ Layout (only what the hot path needs):
   field.py       minimal labelled array standing in for xarray.DataArray
   finitediffs.py FiniteDiff / deriv / deriv2 / padBCs: one HIP launch per operator (reference xinvert/finitediffs.py)
   utils.py       loop_noncore (reference xinvert/utils.py)
+  tridiag.py     trace / traceCyclic: batched tridiagonal direct solves, one system per lane (reference xinvert/numbas.py)
   multigrid.py   invert_MultiGrid: coarse-to-fine SOR solves, HIP restriction / prolongation (reference xinvert/apps.py)
 """
 from .field import Field                                           # noqa: F401
@@ -25,5 +26,6 @@ from .apps import (invert_Poisson, invert_Stommel, invert_StommelMunk, invert_Gi
 from .utils import loop_noncore                                    # noqa: F401
 from .finitediffs import FiniteDiff, deriv, deriv2, padBCs, DeviceField   # noqa: F401
 from .multigrid import invert_MultiGrid                             # noqa: F401
+from .tridiag import trace, traceCyclic                             # noqa: F401
 
 __version__ = '0.1.0'

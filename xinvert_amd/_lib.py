@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get('XINV_SO') or os.path.join(HERE, 'libxinv_hip.so')
 
 BC_CODES = {'fixed': 0, 'extend': 1, 'periodic': 2}
-PATH_AUTO, PATH_COLOUR, PATH_FUSED, PATH_WAVE1D = 0, 1, 2, 4
+PATH_AUTO, PATH_COLOUR, PATH_FUSED, PATH_WAVE1D, PATH_DIRECT1D = 0, 1, 2, 4, 5
 PREP_MASK_NAN, PREP_MASK_VALUE, PREP_ROWSCALE, PREP_S_ZERO, PREP_DEMASK = 1, 2, 4, 8, 16     # XINV_PREP_*
 MAX_DEVICES = 16                      # XINV_MAX_DEVICES
 
@@ -72,6 +72,7 @@ EXPORTS = [
     'xinv_standard_1d_f64', 'xinv_standard_1d_f64_batched', 'xinv_standard_1d_f64_dev',
     'xinv_gm_flow_f64_dev',
     'xinv_abs_norm_f64_dev',
+    'xinv_tridiag_f64', 'xinv_tridiag_f64_dev',
     'xinv_fd_f64', 'xinv_fd_f64_dev',
     'xinv_mg_restrict_f64_dev', 'xinv_mg_prolong_f64_dev',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
@@ -115,6 +116,9 @@ def load():
     fd_args = [_pvp, _int, _pvp, _int, _int, _ip, _int, _int, _ip, _dp, _vp, _i64, _int, _i64]
     L.xinv_fd_f64.argtypes = fd_args
     L.xinv_fd_f64_dev.argtypes = fd_args + [_vp]
+    # tridiagonal systems: x, a, b, c, d, a0, cn, nbatch, strides, n (host pointers; _dev: addresses, + stream)
+    L.xinv_tridiag_f64.argtypes = [_dp] * 7 + [_i64, _ip, _i64]
+    L.xinv_tridiag_f64_dev.argtypes = [_vp] * 7 + [_i64, _ip, _i64, _vp]
     # multigrid transfers: restrict(fine, coarse, nbatch, ndim, fshape, ratio, undef, stream);
     # prolong(coarse, fine, force, nbatch, ndim, cshape, fshape, idx, w, keep_edges, undef, stream)
     L.xinv_mg_restrict_f64_dev.argtypes = [_vp, _vp, _i64, _int, _ip, _ip, _f64, _vp]

@@ -52,6 +52,8 @@ UNITS = [
     ('xinv_tu_bih', 'xinv_tu_bih.hip', ['-mllvm', '-amdgpu-sched-strategy=max-ilp']),
     # the 1-D standard form, register-resident (k_std1d: one member per wavefront or workgroup)
     ('xinv_tu_std1d', 'xinv_tu_std1d.hip', []),
+    # tridiagonal direct solver (trace, traceCyclic, XINV_PATH_DIRECT1D): one system per lane (k_tridiag)
+    ('xinv_tu_tridiag', 'xinv_tu_tridiag.hip', []),
     # finite differences (FiniteDiff, deriv, deriv2): one streaming launch per call (k_fd)
     ('xinv_tu_fd', 'xinv_tu_fd.hip', []),
     # multigrid grid transfers (invert_MultiGrid): k_mg_restrict, k_mg_prolong
@@ -80,9 +82,14 @@ def hipcc():
     raise RuntimeError('hipcc not found')
 
 
+def _abi_headers():
+    """include/xinv.h and the header it includes (xinv_trace.h: the tridiagonal solver's prototypes)."""
+    return [os.path.join(HERE, '..', 'include', f) for f in ('xinv.h', 'xinv_trace.h')]
+
+
 def _headers():
     hs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.h')]
-    hs.append(os.path.join(HERE, '..', 'include', 'xinv.h'))
+    hs += _abi_headers()
     return hs
 
 
@@ -97,12 +104,12 @@ def _stamp(src, flags):
 
 
 def source_hash():
-    """Content hash (16 hex digits) of everything the library is built from: every file of csrc/ and include/xinv.h.
+    """Content hash (16 hex digits) of everything the library is built from: every file of csrc/ and include/xinv.h with the header it includes.
     profiles/traffic.json entries carry the hash of the tree they were profiled on; bench.py reports a counter figure
     only while it still matches (a kernel change that forgets to re-profile must not carry stale bytes forward)."""
     h = hashlib.sha256()
     files = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.h', '.hip'))]
-    files.append(os.path.join(HERE, '..', 'include', 'xinv.h'))
+    files += _abi_headers()
     for f in files:
         h.update(os.path.basename(f).encode())
         with open(f, 'rb') as fh:

@@ -24,7 +24,9 @@ _undeftmp = -9.99e8
 
 def inv_standard1D(A, B, F, S, dims, iParams):
     """d/dx(A dS/dx) + B S = F along one dim   (reference core.py:234-291; GeoAdjustment, RefStateSWM).
-    Every slice is one member of ONE batched call (single device, float64): the register-resident kernel k_std1d."""
+    Every slice is one member of ONE batched call (single device, float64): the register-resident kernel k_std1d, or --
+    iParams['method'] = 'direct' -- one tridiagonal solve per member (XINV_PATH_DIRECT1D: the fixed point of the sweeps;
+    optArg, mxLoop and tolerance play no part, flags = [overflow, 0, 0])."""
     if len(dims) != 1:
         raise Exception('1 dimensions are needed for inversion')
     return _solve('std1d', (A, B), F, S, dims, iParams)
@@ -136,6 +138,17 @@ def _prep_coef(c, F, perm, core_shape, nbatch, allow_null=False):
     return _prep_coef(t, F, perm, core_shape, nbatch, allow_null)
 
 
+def _method(kind, iParams):
+    """iParams['method']: 'sor' (default) or 'direct', which only the 1-D standard form has."""
+    method = iParams.get('method', 'sor')
+    if method not in ('sor', 'direct'):
+        raise Exception("iParams['method'] must be 'sor' or 'direct', got %r" % (method,))
+    if method == 'direct' and kind != 'std1d':
+        raise Exception("iParams['method'] = 'direct' is available for the 1-D standard form only (inv_standard1D, "
+                        "invert_GeoAdjustment, invert_RefStateSWM), not for %s" % forms.FORMS[kind].inv)
+    return method
+
+
 _KIND_OF = {f.inv: k for k, f in forms.FORMS.items() if f.resident}
 
 
@@ -151,6 +164,7 @@ class Resident:
     def __init__(self, inv_name, coefs, F, S, dims, iParams):
         from .resident import ResidentProblem
         kind = _KIND_OF[inv_name]
+        _method(kind, iParams)
         if not isinstance(F, Field) or not isinstance(S, Field):
             raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
         self.F, self.dims = F, dims
@@ -330,6 +344,7 @@ def _result_empty(shape, dtype, iParams):
 
 
 def _solve(kind, coefs, F, S, dims, iParams):
+    direct = _method(kind, iParams) == 'direct'
     if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
         raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
     perm, bdims, bshape = _batch_layout(F, dims)
@@ -397,7 +412,7 @@ def _solve(kind, coefs, F, S, dims, iParams):
     f32_mask = sum(1 << k for k, a_ in enumerate(arrs) if a_ is not None and a_.dtype == np.float32)
     assert bool(f32_mask & 1) == bool(f32_out) and bool(f32_mask >> (len(coefs) + 1)) == bool(f32_in), f32_mask
     opt = _lib.options(device=int(iParams.get('device', -1)),
-                       path=int(iParams.get('engine_path', 0)),
+                       path=_lib.PATH_DIRECT1D if direct else int(iParams.get('engine_path', 0)),
                        sweeps_per_launch=int(iParams.get('sweeps_per_launch', 0)),
                        check_every=int(iParams.get('check_every', 0)), rowconst_mask=rowconst,
                        host_chunk=int(iParams.get('host_chunk', 0)),
@@ -431,6 +446,6 @@ def _solve(kind, coefs, F, S, dims, iParams):
         for m, idx in enumerate(sels):
             info = _info(dict(zip(bdims, idx)))
             tail = ' (overflows!)' if flags[m, 0] else ''
-            print(info + ' loops {0:4.0f} and tolerance is {1:e}'.format(flags[m, 2], flags[m, 1])
-                  + tail)
+            print(info + (' direct solve' if direct else
+                          ' loops {0:4.0f} and tolerance is {1:e}'.format(flags[m, 2], flags[m, 1])) + tail)
     return S

@@ -70,6 +70,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_sweep.h"       /* sweep loop, finalise, device-pointer solve, resident plans */
 #include "xinv_hostptr.h"     /* host-pointer pipeline, in-call multi-GPU split */
 #include "xinv_std1d_host.h"   /* 1-D standard form: register-resident solve (k_std1d) */
+#include "xinv_tridiag_host.h" /* trace / traceCyclic and the direct 1-D solve (k_tridiag) */
 #include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
 #include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
 
@@ -137,6 +138,8 @@ static int run_form(int how, int kind, xinv_plan **plan, double *S, const double
                     void *stream)
 {
     if (how != RUN_SINGLE && !strides) return fail_arg("null strides");
+    if (opt && opt->path == XINV_PATH_DIRECT1D)
+        return fail_arg("XINV_PATH_DIRECT1D: the direct solve exists for the 1-D standard form only");
     Problem p = mk_problem(kind, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc, mxLoop, tolerance);
     GUARD(how == RUN_PLAN ? plan_create(plan, p, opt, (hipStream_t)stream)
           : how == RUN_DEV ? solve_dev(p, flags, opt, (hipStream_t)stream) : solve_host(p, flags, opt))
@@ -485,6 +488,30 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
     if (!strides) return fail_arg("null strides");
     Std1dProblem p = mk_std1d(S, A, B, F, nbatch, strides, xc, BCx, delxSqr, optArg, undef, mxLoop, tolerance);
     GUARD(std1d_solve_dev(p, flags, opt, (hipStream_t)stream))
+}
+
+// ---- tridiagonal systems (k_tridiag: numbas.trace / traceCyclic) --------------------------------------------------
+static TridiagCall mk_tridiag(double *x, const double *a, const double *b, const double *c, const double *d,
+                              const double *a0, const double *cn, int64_t nbatch, const int64_t *strides, int64_t n)
+{
+    TridiagCall t;
+    memset(&t, 0, sizeof t);
+    t.x = x; t.a = a; t.b = b; t.c = c; t.d = d; t.a0 = a0; t.cn = cn; t.nbatch = nbatch; t.n = n;
+    if (strides)
+        for (int q = 0; q < (a0 && cn ? 7 : 5); q++) t.s[q] = strides[q];
+    return t;
+}
+
+int xinv_tridiag_f64(double *x, const double *a, const double *b, const double *c, const double *d, const double *a0,
+                     const double *cn, int64_t nbatch, const int64_t *strides, int64_t n)
+{
+    GUARD(tridiag_solve_host(mk_tridiag(x, a, b, c, d, a0, cn, nbatch, strides, n), strides))
+}
+
+int xinv_tridiag_f64_dev(double *x, const double *a, const double *b, const double *c, const double *d, const double *a0,
+                         const double *cn, int64_t nbatch, const int64_t *strides, int64_t n, void *stream)
+{
+    GUARD(tridiag_solve_dev(mk_tridiag(x, a, b, c, d, a0, cn, nbatch, strides, n), strides, (hipStream_t)stream))
 }
 
 // ---- finite differences (k_fd) ----------------------------------------------------------------------------------

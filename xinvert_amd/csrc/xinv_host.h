@@ -307,6 +307,12 @@ struct Workspace {
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;              // k_pipe2d: per-row records [nbatch][yc][PIPE_RW]
     double *d_pfac = nullptr; size_t d_pfac_cap = 0;            // k_pipe2d<FusedGen2DQ>: the point-factor stream Q [nbatch][yc][xc]
     void *wd_part = nullptr; size_t wd_part_cap = 0;            // watchdog recovery: partials of the separate norm kernels
+    double *tri = nullptr; size_t tri_cap = 0;                  // k_tridiag: buf1 (cyclic: and the two auxiliary solves) [nbatch][n]
+    int *tri_ovf = nullptr; size_t tri_ovf_cap = 0;             // ... the direct 1-D solve's overflow words [nbatch]
+    int *h_tri_ovf = nullptr; size_t h_tri_ovf_cap = 0;         // ... and their pinned mirror (capacity in words)
+    hipEvent_t ev_tri = nullptr; bool tri_pending = false;      // xinv_tridiag_f64_dev only queues its kernel, which reads and
+                                                                // writes `tri` until it ends: an event the workspace owns sits
+                                                                // behind it (tri_wait: the next user of `tri` waits on it)
     StageRing ring_up, ring_down;                               // host-pointer entries: the library's pinned staging
 };
 

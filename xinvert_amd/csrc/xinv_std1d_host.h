@@ -18,12 +18,15 @@ struct Std1dProblem {
     double tolerance;
 };
 
+// XINV_PATH_DIRECT1D (xinv_tridiag_host.h): the fixed point of the sweeps from one tridiagonal solve per member
+static int std1d_direct_run(const Std1dProblem &p, double *flags, const xinv_options &o, hipStream_t st);
+
 static int std1d_validate(const Std1dProblem &p, const double *flags, const xinv_options &o)
 {
     if (!p.S || !p.A || !p.B || !p.F || !flags) return fail_arg("null array or flags");
     if (p.nbatch < 1) return fail_arg("nbatch < 1");
     if (p.xc < 3) return fail_arg("the 1-D form needs xc >= 3");
-    if (p.xc > XINV_STD1D_MAX_XC) {
+    if (p.xc > XINV_STD1D_MAX_XC && o.path != XINV_PATH_DIRECT1D) {
         char b[160];
         snprintf(b, sizeof b, "the 1-D form holds at most %d points per member (16 wavefronts x 64 lanes x 8), got xc = %lld",
                  XINV_STD1D_MAX_XC, (long long)p.xc);
@@ -46,6 +49,7 @@ static int std1d_validate(const Std1dProblem &p, const double *flags, const xinv
 // The solve on DEVICE arrays, on `st`, with the device already selected.
 static int std1d_run(const Std1dProblem &p, double *flags, const xinv_options &o, hipStream_t st)
 {
+    if (o.path == XINV_PATH_DIRECT1D) return std1d_direct_run(p, flags, o, st);
     int device = 0;
     HIPCHK(hipGetDevice(&device));
     Workspace *ws = get_ws(device);
@@ -135,7 +139,7 @@ static int std1d_solve_dev(const Std1dProblem &p, double *flags, const xinv_opti
     return std1d_run(p, flags, o, st);
 }
 
-// Host arrays: upload (a stride-0 array once), solve, download S.  The arrays are small (one member is at most 64 KiB).
+// Host arrays: upload (a stride-0 array once), solve, download S.  The arrays are small (a member of the sweeps is at most 64 KiB).
 static int std1d_solve_host(const Std1dProblem &hp, double *flags, const xinv_options *opt_in)
 {
     xinv_options o;
