@@ -1,7 +1,7 @@
 """xinv_tridiag_f64_dev only queues its kernel, and the kernel keeps buf1 (cyclic: and the two auxiliary solves) in the
 device's one scratch buffer between its forward and its backward pass.  Solves queued from two streams would run side by
 side and overwrite each other's buf1; the library orders every user of the buffer behind the one before it
-(Workspace::ev_tri, xinv_tridiag_host.h).  Here two streams queue solves on different data back to back -- 64 systems
+(Workspace::tri_user, xinv_host.h).  Here two streams queue solves on different data back to back -- 64 systems
 are ONE workgroup, so two such kernels fit on the device together many times over, and 4000 points keep each running for
 milliseconds while the next call is queued in microseconds -- and every result must be the model's bits."""
 import numpy as np

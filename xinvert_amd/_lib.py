@@ -246,5 +246,16 @@ def hptr(a, f32=False):
     return ctypes.cast(a.ctypes.data, _dp)
 
 
+def dptr(t):
+    """Device address of a torch tensor as the C-ABI takes it (None -> NULL)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def stream_arg(where):
+    """torch's current stream on a device, or on the device of a tensor, as the C-ABI takes it."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(getattr(where, 'device', where)).cuda_stream)
+
+
 def strides_arg(vals):
     return (ctypes.c_int64 * len(vals))(*[int(v) for v in vals])

@@ -451,8 +451,8 @@ def cal_flow_gm_device(S_dev_ptr, u_dev_ptr, v_dev_ptr, nbatch, lat_or_y, lon_or
     vp = ctypes.c_void_p
     sp = vp(stream) if stream else None
     rc = L.xinv_gm_flow_f64_dev(vp(S_dev_ptr), vp(u_dev_ptr), vp(v_dev_ptr), int(nbatch), yv.size, xv.size,
-                                vp(ty.data_ptr()), vp(tx.data_ptr()), int(yuni), int(xuni),
-                                vp(tr.data_ptr()), float(deg2m), int(latlon), sp)
+                                _lib.dptr(ty), _lib.dptr(tx), int(yuni), int(xuni),
+                                _lib.dptr(tr), float(deg2m), int(latlon), sp)
     _lib.check(rc)
 
 

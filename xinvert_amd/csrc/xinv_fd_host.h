@@ -150,33 +150,25 @@ static int fd_run_host(const FdCall &hc)
     int64_t elems = 0, nblocks = 0;
     int rc = fd_args(hc, a, &elems, &nblocks);          // (argument checks before any allocation)
     if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t fb = (size_t)elems * sizeof(double);
-    const size_t tb = (size_t)hc.ntab * sizeof(double);
-    char *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, (size_t)(hc.nin + hc.nout) * fb + tb + 64));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{d};
+    PlainStage stage;
+    if ((rc = stage.open((size_t)(hc.nin + hc.nout) * (size_t)elems * sizeof(double) + (size_t)hc.ntab * sizeof(double) + 64)))
+        return rc;
     const double *din[XINV_FD_MAXIN];
     double *dout[XINV_FD_MAXT];
-    hipStream_t st = nullptr;
     for (int k = 0; k < hc.nin; ++k) {
-        din[k] = (const double *)(d + k * fb);
-        HIPCHK(hipMemcpyAsync((void *)din[k], hc.in[k], fb, hipMemcpyHostToDevice, st));
+        double *at = stage.carve(elems);
+        if ((rc = stage.up(at, hc.in[k], elems))) return rc;
+        din[k] = at;
     }
-    for (int k = 0; k < hc.nout; ++k) dout[k] = (double *)(d + (hc.nin + k) * fb);
-    double *dtab = (double *)(d + (hc.nin + hc.nout) * fb);
-    if (tb) HIPCHK(hipMemcpyAsync(dtab, hc.tab, tb, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < hc.nout; ++k) dout[k] = stage.carve(elems);
+    double *dtab = stage.carve(hc.ntab);
+    if (hc.ntab && (rc = stage.up(dtab, hc.tab, hc.ntab))) return rc;
     FdCall c = hc;
     c.in = din; c.out = dout; c.tab = dtab;
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = fd_run_dev(c, st))) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    for (int k = 0; k < hc.nout; ++k) HIPCHK(hipMemcpyAsync(hc.out[k], dout[k], fb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const auto t3 = std::chrono::steady_clock::now();
-    memset(&t_stats, 0, sizeof t_stats);
-    t_stats.h2d_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t_stats.d2h_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-    t_stats.wall_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    return XINV_OK;
+    stage.uploads_queued();
+    if ((rc = fd_run_dev(c, stage.st))) return rc;
+    stage.run_done();
+    for (int k = 0; k < hc.nout; ++k)
+        if ((rc = stage.down(hc.out[k], dout[k], elems))) return rc;
+    return stage.finish(true);
 }

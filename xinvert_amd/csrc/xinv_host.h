@@ -264,6 +264,31 @@ static int bind_thread_to_device_node(int device)
 }
 
 // ------------------------------------------------------------------ per-device workspace
+// An event the WORKSPACE owns, recorded behind work a call returns with still queued on its caller's stream.  Whoever uses
+// the same buffers next makes ITS stream wait for the event (no host wait, no handle of the earlier caller's stream: that
+// stream may be gone by now) -- or, `host`, the calling thread: before a buffer is freed.  A stream wait orders only `st`
+// (another stream must wait again; waiting on an event that has completed costs nothing), so the mark stays until a host
+// wait.  Used under the workspace's lock.
+struct Behind {
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    int wait(hipStream_t st, bool host = false)
+    {
+        if (!pending) return XINV_OK;
+        if (host) HIPCHK(hipEventSynchronize(ev));
+        else HIPCHK(hipStreamWaitEvent(st, ev, 0));
+        if (host) pending = false;
+        return XINV_OK;
+    }
+    int mark(hipStream_t st)
+    {
+        if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev, st));
+        pending = true;
+        return XINV_OK;
+    }
+};
+
 // Grown on demand, reused across solves (no hipMalloc in steady state).
 #define XINV_MAX_LANES 4
 #define XINV_MAX_INFLIGHT 6          /* host-pointer entries: chunk solves in flight on one device (workspace slots 0 .. 5) */
@@ -275,10 +300,10 @@ struct Workspace {
                                                         // host-pointer call can be in flight on the device at once (solve_host_one)
     std::recursive_mutex busy;                          // one solve at a time per device
     double *S2 = nullptr; size_t S2_cap = 0;            // ping-pong twin of S (fused path)
-    hipEvent_t ev_tail = nullptr; bool tail_pending = false;   // a plan solve's redo pass and last copy out of S2 / S3 may still
-                                                        // be in flight (xinv_plan_solve: S completes in stream order): an event
-                                                        // the WORKSPACE owns sits behind them -- the caller may destroy its stream
-                                                        // (tail_wait: whoever touches S2 / S3 or a plan's buffers next waits on it)
+    Behind tail;                                        // a plan solve's redo pass and last copy out of S2 / S3 may still be in
+                                                        // flight (xinv_plan_solve: S completes in stream order) -- the caller may
+                                                        // destroy its stream; whoever touches S2 / S3, the control blocks or a
+                                                        // plan's buffers next waits on it
     XinvCtl *ctl = nullptr; size_t ctl_cap = 0;
     void *partials = nullptr; size_t partials_cap = 0;  // norm partials
     size_t partials_half = 0;                           // lagged norm: byte offset of the odd launches' buffer
@@ -286,7 +311,7 @@ struct Workspace {
     int *dflag = nullptr;
     int *d_hook = nullptr;                              // test-hooks build: {tile, launch tag, member} (FusedArgs::dbg)
     int *dflags16 = nullptr, *hflags16 = nullptr;      // x-uniform detection flags
-    XinvCtl *hctl = nullptr; size_t hctl_cap = 0;       // pinned mirror of ctl
+    XinvCtl *hctl = nullptr; size_t hctl_cap = 0;       // pinned mirror of ctl: two slots (every pinned capacity is in bytes)
     unsigned *hmail = nullptr; unsigned mail_seq = 0;   // pinned sequence word of k_ctl_mail (short solves: the host spins on it)
     int *hflag = nullptr;
     hipEvent_t ev0[2] = {nullptr, nullptr}, ev1[2] = {nullptr, nullptr}, evc[2] = {nullptr, nullptr};
@@ -309,10 +334,9 @@ struct Workspace {
     void *wd_part = nullptr; size_t wd_part_cap = 0;            // watchdog recovery: partials of the separate norm kernels
     double *tri = nullptr; size_t tri_cap = 0;                  // k_tridiag: buf1 (cyclic: and the two auxiliary solves) [nbatch][n]
     int *tri_ovf = nullptr; size_t tri_ovf_cap = 0;             // ... the direct 1-D solve's overflow words [nbatch]
-    int *h_tri_ovf = nullptr; size_t h_tri_ovf_cap = 0;         // ... and their pinned mirror (capacity in words)
-    hipEvent_t ev_tri = nullptr; bool tri_pending = false;      // xinv_tridiag_f64_dev only queues its kernel, which reads and
-                                                                // writes `tri` until it ends: an event the workspace owns sits
-                                                                // behind it (tri_wait: the next user of `tri` waits on it)
+    int *h_tri_ovf = nullptr; size_t h_tri_ovf_cap = 0;         // ... and their pinned mirror
+    Behind tri_user;                                            // xinv_tridiag_f64_dev only queues its kernel, which reads and
+                                                                // writes `tri` until it ends: the next user of `tri` waits on it
     StageRing ring_up, ring_down;                               // host-pointer entries: the library's pinned staging
 };
 
@@ -336,6 +360,20 @@ static int ensure_dev(T **p, size_t *cap, size_t need_bytes)
     if (*cap >= need_bytes && *p) return XINV_OK;
     if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; *cap = 0; }
     HIPCHK(hipMalloc((void **)p, need_bytes));
+    *cap = need_bytes;
+    return XINV_OK;
+}
+
+// ... and its pinned counterpart (`flags` of hipHostMalloc).  The old block is forgotten before it is freed: a failed
+// growth leaves an empty buffer, never a pointer to freed memory.
+template <class T>
+static int ensure_pinned(T **p, size_t *cap, size_t need_bytes, unsigned flags)
+{
+    if (*cap >= need_bytes && *p) return XINV_OK;
+    T *old = *p;
+    *p = nullptr; *cap = 0;
+    if (old) HIPCHK(hipHostFree(old));
+    HIPCHK(hipHostMalloc((void **)p, need_bytes, flags));
     *cap = need_bytes;
     return XINV_OK;
 }
@@ -516,3 +554,51 @@ struct Pinned {                                     // host ranges registered fo
     }
 };
 
+// The plain host-pointer entries of the side families (1-D form, tridiagonal systems, finite differences): one device block
+// allocated and freed per call, pageable copies on the null stream, and the call's three times.  The arrays are carved out
+// of the block in order; the clock starts where the stage is declared.
+struct PlainStage {
+    typedef std::chrono::steady_clock clock;
+    char *base = nullptr, *next = nullptr;
+    hipStream_t st = nullptr;
+    clock::time_point t0 = clock::now(), t1, t2;
+    ~PlainStage() { if (base) (void)hipFree(base); }
+    int open(size_t bytes) { HIPCHK(hipMalloc((void **)&base, bytes)); next = base; return XINV_OK; }
+    double *carve(int64_t n) { double *p = (double *)next; next += (size_t)n * sizeof(double); return p; }
+    int up(double *dev, const double *host, int64_t n)
+    {
+        HIPCHK(hipMemcpyAsync(dev, host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        return XINV_OK;
+    }
+    int down(double *host, const double *dev, int64_t n)
+    {
+        HIPCHK(hipMemcpyAsync(host, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        return XINV_OK;
+    }
+    // `rows` rows of `len` elements, `stride` elements apart on the host (one row: any stride), packed on the device
+    int up_rows(double *dev, const double *host, int64_t rows, int64_t len, int64_t stride)
+    {
+        const size_t row = (size_t)len * sizeof(double), pitch = (size_t)(rows > 1 ? stride : len) * sizeof(double);
+        HIPCHK(hipMemcpy2DAsync(dev, row, host, pitch, row, (size_t)rows, hipMemcpyHostToDevice, st));
+        return XINV_OK;
+    }
+    int down_rows(double *host, const double *dev, int64_t rows, int64_t len, int64_t stride)
+    {
+        const size_t row = (size_t)len * sizeof(double), pitch = (size_t)(rows > 1 ? stride : len) * sizeof(double);
+        HIPCHK(hipMemcpy2DAsync(host, pitch, dev, row, row, (size_t)rows, hipMemcpyDeviceToHost, st));
+        return XINV_OK;
+    }
+    void uploads_queued() { t1 = clock::now(); }
+    void run_done() { t2 = clock::now(); }
+    // after the downloads: drains the stream; `reset`: the statistics hold nothing but the three times
+    int finish(bool reset)
+    {
+        HIPCHK(hipStreamSynchronize(st));
+        const auto t3 = clock::now();
+        if (reset) memset(&t_stats, 0, sizeof t_stats);
+        t_stats.h2d_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t_stats.d2h_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
+        t_stats.wall_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
+        return XINV_OK;
+    }
+};

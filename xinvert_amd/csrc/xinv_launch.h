@@ -579,11 +579,7 @@ static int issue_strip_active(const Problem &p, Workspace *ws, hipStream_t st, i
     const int64_t cells = yc * nstrip;
     int rc = ensure_dev(&ws->d_act, &ws->d_act_cap, (size_t)(nb * cells));
     if (rc) return rc;
-    if (ws->h_act_cap < (size_t)(nb * cells)) {
-        if (ws->h_act) HIPCHK(hipHostFree(ws->h_act));
-        HIPCHK(hipHostMalloc((void **)&ws->h_act, (size_t)(nb * cells), hipHostMallocDefault));
-        ws->h_act_cap = (size_t)(nb * cells);
-    }
+    if ((rc = ensure_pinned(&ws->h_act, &ws->h_act_cap, (size_t)(nb * cells), hipHostMallocDefault))) return rc;
     StripActArgs sa;
     sa.f = p.c[fi]; sa.sf = p.sc[fi]; sa.yc = yc; sa.xc = p.xc; sa.nstrip = nstrip; sa.UW = UW;
     sa.undef = p.sc_.undef; sa.act = ws->d_act;
@@ -712,11 +708,7 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
     const size_t nints = (size_t)nb * ((size_t)ntl + nskip);
     rc = ensure_dev(&ws->d_list, &ws->d_list_cap, nints * sizeof(int));
     if (rc) return rc;
-    if (ws->h_list_cap < nints * sizeof(int)) {
-        if (ws->h_list) HIPCHK(hipHostFree(ws->h_list));
-        HIPCHK(hipHostMalloc((void **)&ws->h_list, nints * sizeof(int), hipHostMallocDefault));
-        ws->h_list_cap = nints * sizeof(int);
-    }
+    if ((rc = ensure_pinned(&ws->h_list, &ws->h_list_cap, nints * sizeof(int), hipHostMallocDefault))) return rc;
     int *hl = ws->h_list, *hs = ws->h_list + (size_t)nb * ntl;
     for (int64_t m = 0; m < nb; m++) {
         std::vector<int> &am = act[(size_t)m];

@@ -1,6 +1,6 @@
 // xinv_std1d_host.h -- host driver of the 1-D standard form (k_std1d, xinv_std1d.h): argument checks, the chain of
 // bounded launches with its polls of the pinned control-block mirror, and the host-pointer staging.  Included by
-// xinv_hip.hip only, after xinv_sweep.h (ensure_mirror, member_flags).
+// xinv_hip.hip only, after xinv_sweep.h (ensure_mirror, member_flags, ws_ready).
 #pragma once
 #include "xinv_std1d.h"
 
@@ -54,7 +54,7 @@ static int std1d_run(const Std1dProblem &p, double *flags, const xinv_options &o
     HIPCHK(hipGetDevice(&device));
     Workspace *ws = get_ws(device);
     std::lock_guard<std::recursive_mutex> lock(ws->busy);
-    int rc = tail_wait(ws, st);                          // (a previous plan solve's tail may still read the control blocks)
+    int rc = ws->tail.wait(st);                          // (a previous plan solve's tail may still read the control blocks)
     if (rc) return rc;
     rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)p.nbatch * sizeof(XinvCtl));
     if (rc) return rc;
@@ -124,6 +124,14 @@ static int std1d_run(const Std1dProblem &p, double *flags, const xinv_options &o
     return XINV_OK;
 }
 
+// `device` (xinv_options.device) selected for the scope of `dg`, its workspace ready for a solve
+static int std1d_device(DeviceGuard &dg, int device)
+{
+    HIPCHK(dg.select(device));
+    HIPCHK(hipGetDevice(&device));
+    return ws_ready(get_ws(device));
+}
+
 static int std1d_solve_dev(const Std1dProblem &p, double *flags, const xinv_options *opt_in, hipStream_t st)
 {
     xinv_options o;
@@ -131,11 +139,7 @@ static int std1d_solve_dev(const Std1dProblem &p, double *flags, const xinv_opti
     int rc = std1d_validate(p, flags, o);
     if (rc) return rc;
     DeviceGuard dg;
-    HIPCHK(dg.select(o.device));
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    rc = ws_ready(get_ws(device));
-    if (rc) return rc;
+    if ((rc = std1d_device(dg, o.device))) return rc;
     return std1d_run(p, flags, o, st);
 }
 
@@ -146,46 +150,24 @@ static int std1d_solve_host(const Std1dProblem &hp, double *flags, const xinv_op
     fill_options(o, opt_in);
     int rc = std1d_validate(hp, flags, o);
     if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard dg;
-    HIPCHK(dg.select(o.device));
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    rc = ws_ready(get_ws(device));
-    if (rc) return rc;
+    PlainStage stage;
+    if ((rc = std1d_device(dg, o.device))) return rc;
     const int64_t xc = hp.xc, nb = hp.nbatch;
-    const size_t row = (size_t)xc * sizeof(double);
     auto rows = [&](int64_t s) { return (s == 0 || nb == 1) ? (int64_t)1 : nb; };
-    const int64_t nS = nb, nA = rows(hp.sA), nB = rows(hp.sB), nF = rows(hp.sF);
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, (size_t)(nS + nA + nB + nF) * row));
-    struct Free { double *p; ~Free() { if (p) (void)hipFree(p); } } guard{d};
+    const int64_t nA = rows(hp.sA), nB = rows(hp.sB), nF = rows(hp.sF);
+    if ((rc = stage.open((size_t)(nb + nA + nB + nF) * (size_t)xc * sizeof(double)))) return rc;
+    double *dS = stage.carve(nb * xc), *dA = stage.carve(nA * xc), *dB = stage.carve(nB * xc), *dF = stage.carve(nF * xc);
     Std1dProblem p = hp;
-    p.S = d;
-    p.A = d + nS * xc;
-    p.B = p.A + nA * xc;
-    p.F = p.B + nB * xc;
+    p.S = dS; p.A = dA; p.B = dB; p.F = dF;
     p.sS = xc; p.sA = nA > 1 ? xc : 0; p.sB = nB > 1 ? xc : 0; p.sF = nF > 1 ? xc : 0;
-    hipStream_t st = nullptr;
-    auto up = [&](double *dst, const double *src, int64_t s, int64_t n) -> int {
-        HIPCHK(hipMemcpy2DAsync(dst, row, src, (size_t)(n > 1 ? s : xc) * sizeof(double), row, (size_t)n,
-                                hipMemcpyHostToDevice, st));
-        return XINV_OK;
-    };
-    if ((rc = up(p.S, hp.S, hp.sS, nS)) || (rc = up((double *)p.A, hp.A, hp.sA, nA)) ||
-        (rc = up((double *)p.B, hp.B, hp.sB, nB)) || (rc = up((double *)p.F, hp.F, hp.sF, nF)))
+    if ((rc = stage.up_rows(dS, hp.S, nb, xc, hp.sS)) || (rc = stage.up_rows(dA, hp.A, nA, xc, hp.sA)) ||
+        (rc = stage.up_rows(dB, hp.B, nB, xc, hp.sB)) || (rc = stage.up_rows(dF, hp.F, nF, xc, hp.sF)))
         return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    rc = std1d_run(p, flags, o, st);
-    if (rc) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpy2DAsync(hp.S, (size_t)(nb > 1 ? hp.sS : xc) * sizeof(double), p.S, row, row, (size_t)nb,
-                            hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const auto t3 = std::chrono::steady_clock::now();
-    t_stats.h2d_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t_stats.d2h_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-    t_stats.wall_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    t_stats.host_chunks = 1;
+    stage.uploads_queued();
+    if ((rc = std1d_run(p, flags, o, stage.st))) return rc;
+    stage.run_done();
+    if ((rc = stage.down_rows(hp.S, dS, nb, xc, hp.sS)) || (rc = stage.finish(false))) return rc;
+    t_stats.host_chunks = 1;                             // (beside what std1d_run wrote)
     return XINV_OK;
 }

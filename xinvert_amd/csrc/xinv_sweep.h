@@ -48,19 +48,6 @@ static int launch_planned(const Problem &p, const Plan &pl, Workspace *ws, hipSt
                                     : launch_fused(p, pl, k, src, dst, ws, s, member0, nmem, force, no_ctl, lag_tag, lag_out, lag_prev);
 }
 
-// A stream-ordered plan solve returns with its redo pass and the copy of the final state out of S2 / S3 still queued
-// (finalise); the workspace's own event sits behind them.  Whoever writes those buffers or a plan's records next -- the
-// next solve, a plan build / refresh -- makes ITS stream wait for the event (no host wait, no handle of the earlier
-// caller's stream: that stream may be gone by now); plan_free waits on the host before it frees.
-static int tail_wait(Workspace *ws, hipStream_t st, bool host = false)
-{
-    if (!ws->tail_pending) return XINV_OK;
-    if (host) HIPCHK(hipEventSynchronize(ws->ev_tail));
-    else HIPCHK(hipStreamWaitEvent(st, ws->ev_tail, 0));
-    if (host) ws->tail_pending = false;                  // (a stream wait orders only `st`: another stream must wait again;
-    return XINV_OK;                                      //  waiting on an event that has completed costs nothing)
-}
-
 // sweep loop in lanes (run_sweeps): how many independent launch chains the batch is cut into.
 // Measured with 1 and 2 lanes on one box (profiles/r04_lanes.txt; XINV_LANES=n forces n, 0 or 1 = off):
 //   3600x1800 x 2/3/4/6/8/12/16/32 members  +6 +7 +6 +8 +10 +5 +8 +1.5 %      (5 members: 0)
@@ -96,12 +83,7 @@ static size_t partial_bytes(const Problem &p, const Plan &pl)
 // the pinned mirror of `nctl` control blocks for the host's polls: two slots, polling is pipelined
 static int ensure_mirror(Workspace *ws, int64_t nctl)
 {
-    if (ws->hctl_cap >= (size_t)nctl) return XINV_OK;
-    if (ws->hctl) HIPCHK(hipHostFree(ws->hctl));
-    ws->hctl = nullptr; ws->hctl_cap = 0;
-    HIPCHK(hipHostMalloc((void **)&ws->hctl, 2 * (size_t)nctl * sizeof(XinvCtl), XINV_HOST_COHERENT));
-    ws->hctl_cap = (size_t)nctl;
-    return XINV_OK;
+    return ensure_pinned(&ws->hctl, &ws->hctl_cap, 2 * (size_t)nctl * sizeof(XinvCtl), XINV_HOST_COHERENT);
 }
 
 // Behind the previous plan solve's tail (its copy into its caller's S reads S2 / S3): control blocks of `nctl` members
@@ -112,7 +94,7 @@ static int solve_workspace(Workspace *ws, hipStream_t st, int64_t nctl, bool mir
                            int64_t span, bool s3)
 {
     int rc;
-    if ((rc = tail_wait(ws, st)) || (rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)nctl * sizeof(XinvCtl)))) return rc;
+    if ((rc = ws->tail.wait(st)) || (rc = ensure_dev(&ws->ctl, &ws->ctl_cap, (size_t)nctl * sizeof(XinvCtl)))) return rc;
     if (mirror && (rc = ensure_mirror(ws, nctl))) return rc;
     ws->partials_half = (pbytes + 255) & ~(size_t)255;
     if ((rc = ensure_dev(&ws->partials, &ws->partials_cap, (two_halves ? 2 : 1) * ws->partials_half))) return rc;
@@ -632,9 +614,7 @@ static int finalise(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t
         //  the copy of the final state into S -- and a redone pass.  A plan solve leaves them in flight: S completes in
         //  stream order, 15-25 us of host wake-up less per solve; the workspace remembers the stream)
         if (stream_ordered && R.lev.size() <= 1) {
-            if (!ws->ev_tail) HIPCHK(hipEventCreateWithFlags(&ws->ev_tail, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ws->ev_tail, st));
-            ws->tail_pending = true;
+            if (int rc = ws->tail.mark(st)) return rc;
         } else HIPCHK(hipStreamSynchronize(st));
         if (R.lev.size() > 1) {                          // timing == 2: the launches that did work (not the no-op tail)
             double mn = 1e300, mx = 0.0, sum = 0.0; int cnt = 0;
@@ -795,7 +775,7 @@ static int plan_build(xinv_plan *h, hipStream_t st)
     Problem p = h->p;
     p.S = kPlanS;
     p.stop.mxLoop = (long long)1 << 40; p.stop.tolerance = 0.0;
-    rc = tail_wait(ws, st);                              // (a queued redo pass may still read this plan's records and lists)
+    rc = ws->tail.wait(st);                              // (a queued redo pass may still read this plan's records and lists)
     if (rc) return rc;
     BufSwap sw(ws, &h->bufs);
     rc = make_plan(p, h->opt, ws, st, h->pl);
@@ -812,7 +792,7 @@ static void plan_free(xinv_plan *h)
     {                                                    // (a stream-ordered solve's redo pass may still read the buffers)
         Workspace *ws = get_ws(h->device);
         std::lock_guard<std::recursive_mutex> lock(ws->busy);
-        (void)tail_wait(ws, nullptr, true);
+        (void)ws->tail.wait(nullptr, true);
     }
     if (h->bufs.d_rowf) (void)hipFree(h->bufs.d_rowf);
     if (h->bufs.d_list) (void)hipFree(h->bufs.d_list);

@@ -35,35 +35,18 @@ static int tridiag_validate(const TridiagCall &c, const int64_t *strides)
     return XINV_OK;
 }
 
-// A queued xinv_tridiag_f64_dev solve may still be using ws->tri, on any stream (it returns once its kernel is queued).
-// Whoever uses the buffer next orders `st` behind it -- or, `host`, the calling thread: before the buffer is freed to grow.
-// The same shape as tail_wait (xinv_sweep.h): a stream wait orders only `st`, so the mark stays until a host wait.
-static int tri_wait(Workspace *ws, hipStream_t st, bool host)
-{
-    if (!ws->tri_pending) return XINV_OK;
-    if (host) HIPCHK(hipEventSynchronize(ws->ev_tri));
-    else HIPCHK(hipStreamWaitEvent(st, ws->ev_tri, 0));
-    if (host) ws->tri_pending = false;
-    return XINV_OK;
-}
-
-// the forward pass's workspace: `arrays` x [nbatch][n] doubles and, `ovf`, one word per member; `st` is the stream the
-// solve will run on, ordered here behind a solve that still uses the buffer
+// the forward pass's workspace: `arrays` x [nbatch][n] doubles and, `ovf`, one word per member.  A queued
+// xinv_tridiag_f64_dev solve may still be using ws->tri, on any stream: `st`, the stream the solve will run on, is ordered
+// behind it here -- or the calling thread, before the buffer is freed to grow.
 static int tridiag_workspace(Workspace *ws, hipStream_t st, int64_t nbatch, int64_t n, int arrays, bool ovf)
 {
     const size_t need = (size_t)arrays * (size_t)nbatch * (size_t)n * sizeof(double);
-    int rc = tri_wait(ws, st, !ws->tri || ws->tri_cap < need);
+    int rc = ws->tri_user.wait(st, !ws->tri || ws->tri_cap < need);
     if (rc) return rc;
     rc = ensure_dev(&ws->tri, &ws->tri_cap, need);
     if (rc || !ovf) return rc;
     if ((rc = ensure_dev(&ws->tri_ovf, &ws->tri_ovf_cap, (size_t)nbatch * sizeof(int)))) return rc;
-    if (ws->h_tri_ovf_cap < (size_t)nbatch) {
-        if (ws->h_tri_ovf) HIPCHK(hipHostFree(ws->h_tri_ovf));
-        ws->h_tri_ovf = nullptr; ws->h_tri_ovf_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&ws->h_tri_ovf, (size_t)nbatch * sizeof(int), hipHostMallocDefault));
-        ws->h_tri_ovf_cap = (size_t)nbatch;
-    }
-    return XINV_OK;
+    return ensure_pinned(&ws->h_tri_ovf, &ws->h_tri_ovf_cap, (size_t)nbatch * sizeof(int), hipHostMallocDefault);
 }
 
 // Device arrays, on `st`, with the device already selected.  Returns with the kernel queued: the lock covers the launch,
@@ -89,10 +72,7 @@ static int tridiag_run_dev(const TridiagCall &c, hipStream_t st)
     a.nbatch = c.nbatch; a.n = c.n;
     xinv_launch_tridiag(a, false, cyc, st);
     HIPCHK(hipGetLastError());
-    if (!ws->ev_tri) HIPCHK(hipEventCreateWithFlags(&ws->ev_tri, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ws->ev_tri, st));
-    ws->tri_pending = true;
-    return XINV_OK;
+    return ws->tri_user.mark(st);
 }
 
 static int tridiag_solve_dev(const TridiagCall &c, const int64_t *strides, hipStream_t st)
@@ -102,15 +82,15 @@ static int tridiag_solve_dev(const TridiagCall &c, const int64_t *strides, hipSt
     return tridiag_run_dev(c, st);
 }
 
-// Host arrays: upload (a shared array once), one solve, download x.  Like std1d_solve_host it is the plain entry: one
-// device block allocated and freed per call, pageable copies on the null stream.  "No hipMalloc in steady state" holds
-// for the device entry and the direct path, whose scratch is the workspace; a caller who minds keeps its arrays on the
-// device.
+// Host arrays: upload (a shared array once), one solve, download x.  Like std1d_solve_host it is the plain entry
+// (PlainStage): one device block allocated and freed per call, pageable copies on the null stream.  "No hipMalloc in
+// steady state" holds for the device entry and the direct path, whose scratch is the workspace; a caller who minds keeps
+// its arrays on the device.
 static int tridiag_solve_host(const TridiagCall &hc, const int64_t *strides)
 {
     int rc = tridiag_validate(hc, strides);
     if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    PlainStage stage;
     const int64_t nb = hc.nbatch, n = hc.n;
     const bool cyc = hc.a0 != nullptr;
     const double *src[6] = { hc.a, hc.b, hc.c, hc.d, hc.a0, hc.cn };
@@ -121,36 +101,23 @@ static int tridiag_solve_host(const TridiagCall &hc, const int64_t *strides)
         rows[q] = (nb == 1 || hc.s[1 + q] == 0) ? 1 : nb;
         total += rows[q] * len[q];
     }
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, (size_t)total * sizeof(double)));
-    struct Free { double *p; ~Free() { if (p) (void)hipFree(p); } } guard{d};
-    hipStream_t st = nullptr;
+    if ((rc = stage.open((size_t)total * sizeof(double)))) return rc;
     TridiagCall c = hc;
-    c.x = d; c.s[0] = n;
-    double *at = d + nb * n;
+    c.x = stage.carve(nb * n); c.s[0] = n;
     const double *dev[6] = {};
     for (int q = 0; q < narr; q++) {
+        double *at = stage.carve(rows[q] * len[q]);
+        if ((rc = stage.up_rows(at, src[q], rows[q], len[q], hc.s[1 + q]))) return rc;
         dev[q] = at;
-        const size_t row = (size_t)len[q] * sizeof(double);
-        HIPCHK(hipMemcpy2DAsync(at, row, src[q], (size_t)(rows[q] > 1 ? hc.s[1 + q] : len[q]) * sizeof(double), row,
-                                (size_t)rows[q], hipMemcpyHostToDevice, st));
         c.s[1 + q] = rows[q] > 1 ? len[q] : 0;
-        at += rows[q] * len[q];
     }
     c.a = dev[0]; c.b = dev[1]; c.c = dev[2]; c.d = dev[3];
     if (cyc) { c.a0 = dev[4]; c.cn = dev[5]; }
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = tridiag_run_dev(c, st))) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    HIPCHK(hipMemcpy2DAsync(hc.x, (size_t)(nb > 1 ? hc.s[0] : n) * sizeof(double), d, (size_t)n * sizeof(double),
-                            (size_t)n * sizeof(double), (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const auto t3 = std::chrono::steady_clock::now();
-    memset(&t_stats, 0, sizeof t_stats);
-    t_stats.h2d_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t_stats.d2h_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-    t_stats.wall_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    return XINV_OK;
+    stage.uploads_queued();
+    if ((rc = tridiag_run_dev(c, stage.st))) return rc;
+    stage.run_done();
+    if ((rc = stage.down_rows(hc.x, c.x, nb, n, hc.s[0]))) return rc;
+    return stage.finish(true);
 }
 
 // XINV_PATH_DIRECT1D: the 1-D standard form's fixed point in one launch (std1d_run hands over; `p` holds DEVICE arrays).
@@ -183,7 +150,7 @@ static int std1d_direct_run(const Std1dProblem &p, double *flags, const xinv_opt
     if (timing) HIPCHK(hipEventRecord(e1, st));
     HIPCHK(hipMemcpyAsync(ws->h_tri_ovf, ws->tri_ovf, (size_t)p.nbatch * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    ws->tri_pending = false;                             // (`st` waited on the event, and has drained)
+    ws->tri_user.pending = false;                        // (`st` waited on the event, and has drained)
     for (int64_t m = 0; m < p.nbatch; m++) {
         flags[3 * m] = ws->h_tri_ovf[m] ? 1.0 : 0.0;
         flags[3 * m + 1] = 0.0;

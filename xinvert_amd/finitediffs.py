@@ -248,9 +248,8 @@ class _Call:
         outs = [torch.empty(self.shape, dtype=torch.float64, device=dev) for _ in range(nout)]
         with torch.cuda.device(dev):
             tab = torch.from_numpy(np.concatenate(self.tabs) if self.tabs else np.zeros(1)).to(dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self._call(L.xinv_fd_f64_dev, [t.data_ptr() for t in ins], [t.data_ptr() for t in outs], tab.data_ptr(),
-                       stream)
+            self._call(L.xinv_fd_f64_dev, [_lib.dptr(t) for t in ins], [_lib.dptr(t) for t in outs], _lib.dptr(tab),
+                       _lib.stream_arg(dev))
         return outs
 
     def _call(self, fn, ins, outs, tab, *stream):
@@ -264,9 +263,8 @@ class _Call:
         f64 = ctypes.POINTER(ctypes.c_double)
         args = [ctypes.cast(inp, ctypes.POINTER(vp)), len(ins), ctypes.cast(outp, ctypes.POINTER(vp)), len(outs),
                 len(self.shape), shape.ctypes.data_as(i64), self.mode, len(self.iterm), iterm.ctypes.data_as(i64),
-                dterm.ctypes.data_as(f64), vp(tab), self.ntab, self.mask_axis, self.mask_off]
-        args += [vp(s) if s else None for s in stream]
-        _lib.check(fn(*args))
+                dterm.ctypes.data_as(f64), tab, self.ntab, self.mask_axis, self.mask_off]
+        _lib.check(fn(*args, *stream))
 
 
 # ------------------------------------------------------------------ module functions

@@ -17,7 +17,6 @@ its own:
     except where the ordinary solve keeps its starting value (undefined forcing, the edges of non-periodic dims);
   * a single level (gridNo = 1, ratio = 1, or a grid too small to coarsen) is exactly the app's own call.
 """
-import ctypes
 import inspect
 
 import numpy as np
@@ -159,15 +158,6 @@ def _restrict_param(p, rmap, dims, core_shape):
 
 
 # ------------------------------------------------------------------------------ device transfers
-def _stream(t):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def restrict_dev(fine, ratios, undef):
     """k_mg_restrict on a torch tensor [nbatch, *core] (float64, contiguous) -> the coarse tensor."""
     import torch
@@ -181,9 +171,9 @@ def restrict_dev(fine, ratios, undef):
                       device=fine.device)
     L = _lib.require_gpu()
     with torch.cuda.device(fine.device):
-        _lib.check(L.xinv_mg_restrict_f64_dev(_ptr(fine), _ptr(out),
+        _lib.check(L.xinv_mg_restrict_f64_dev(_lib.dptr(fine), _lib.dptr(out),
                                               int(fine.shape[0]), nd, _lib.strides_arg(fshape),
-                                              _lib.strides_arg(ratios), float(undef), _stream(fine)))
+                                              _lib.strides_arg(ratios), float(undef), _lib.stream_arg(fine)))
     return out
 
 
@@ -211,11 +201,11 @@ def prolong_dev(coarse, fine, tables, keep_edges=0, force=None, undef=_undeftmp)
         ws.append(w.astype(np.float64))
     idx_t = torch.from_numpy(np.concatenate(idx)).to(fine.device)
     w_t = torch.from_numpy(np.concatenate(ws)).to(fine.device)
-    L = _lib.require_gpu()
+    L, ptr = _lib.require_gpu(), _lib.dptr
     with torch.cuda.device(fine.device):
         _lib.check(L.xinv_mg_prolong_f64_dev(
-            _ptr(coarse), _ptr(fine), _ptr(force), int(fine.shape[0]), nd, _lib.strides_arg(cshape),
-            _lib.strides_arg(fshape), _ptr(idx_t), _ptr(w_t), int(keep_edges), float(undef), _stream(fine)))
+            ptr(coarse), ptr(fine), ptr(force), int(fine.shape[0]), nd, _lib.strides_arg(cshape),
+            _lib.strides_arg(fshape), ptr(idx_t), ptr(w_t), int(keep_edges), float(undef), _lib.stream_arg(fine)))
     # (the tables' blocks go back to torch's allocator on return: it reuses them in the order of this stream)
     return fine
 

@@ -122,19 +122,18 @@ class ResidentProblem:
         """The coefficient arrays (or the forcing's mask) were changed in place: re-derive every plan."""
         import torch
         self._join()
-        st = torch.cuda.current_stream(self.dev)
+        st = _lib.stream_arg(self.dev)
         for h in self._plans.values():
-            _lib.check(self.L.xinv_plan_refresh(h, ctypes.c_void_p(st.cuda_stream)))
+            _lib.check(self.L.xinv_plan_refresh(h, st))
 
     def _plan(self, opt, st):
         key = tuple(sorted(opt.items()))
         h = self._plans.get(key)
         if h is None:
             o = _lib.options(device=self.device, rowconst_mask=self.rowconst, **opt)
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
             h = ctypes.c_void_p()
             rc = getattr(self.L, PLAN_FN[self.kind])(
-                ctypes.byref(h), *[ptr(c) for c in self.coefs], self.nb, self.strides, *scalars(self.p),
+                ctypes.byref(h), *[_lib.dptr(c) for c in self.coefs], self.nb, self.strides, *scalars(self.p),
                 ctypes.byref(o), ctypes.c_void_p(st.cuda_stream))
             _lib.check(rc)
             self._plans[key] = h
@@ -155,14 +154,13 @@ class ResidentProblem:
         self.flags[:] = np.array([0., 1., 0.])
         if self.use_plan:
             h = self._plan(opt, st)
-            rc = self.L.xinv_plan_solve_f64_dev(h, ctypes.c_void_p(self.S.data_ptr()), _lib.hptr(self.flags),
+            rc = self.L.xinv_plan_solve_f64_dev(h, _lib.dptr(self.S), _lib.hptr(self.flags),
                                                 int(mxLoop), float(tolerance), ctypes.c_void_p(st.cuda_stream))
             _lib.check(rc)
             return self.flags, _lib.last_stats()
         o = _lib.options(device=self.device, **opt)
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         rc = getattr(self.L, FN[self.kind] + '_dev')(
-            ptr(self.S), *[ptr(c) for c in self.coefs], self.nb, self.strides, *scalars(self.p),
+            _lib.dptr(self.S), *[_lib.dptr(c) for c in self.coefs], self.nb, self.strides, *scalars(self.p),
             _lib.hptr(self.flags), int(mxLoop), float(tolerance), ctypes.byref(o),
             ctypes.c_void_p(st.cuda_stream))
         _lib.check(rc)
@@ -183,7 +181,7 @@ class ResidentProblem:
         nf = int(frames.shape[0])
         fl = np.tile(np.array([0., 1., 0.]), (nf, self.nb, 1))
         h = self._plan(opt, st)
-        rc = self.L.xinv_plan_solve_frames_f64_dev(h, ctypes.c_void_p(self.S.data_ptr()), ctypes.c_void_p(frames.data_ptr()), nf,
+        rc = self.L.xinv_plan_solve_frames_f64_dev(h, _lib.dptr(self.S), _lib.dptr(frames), nf,
                                                    int(self.S.numel()), _lib.hptr(fl), int(mxLoop), float(tolerance),
                                                    ctypes.c_void_p(st.cuda_stream))
         _lib.check(rc)

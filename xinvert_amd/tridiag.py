@@ -76,8 +76,7 @@ def _solve_torch(a, b, c, d, a0, cn):
     if nbatch == 0:
         return x
     L = _lib.require_gpu()
-    ptrs = [v.data_ptr() for v in arrs] + ([v.data_ptr() for v in corners] if cyclic else [None, None])
+    ptrs = [_lib.dptr(v) for v in [x] + arrs + (corners if cyclic else [None, None])]
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.xinv_tridiag_f64_dev(x.data_ptr(), *ptrs, nbatch, _lib.strides_arg([N] + strides), N, st))
+        _lib.check(L.xinv_tridiag_f64_dev(*ptrs, nbatch, _lib.strides_arg([N] + strides), N, _lib.stream_arg(dev)))
     return x
