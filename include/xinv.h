@@ -432,6 +432,40 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
  * which this one includes: a caller of xinv.h has them. */
 #include "xinv_trace.h"
 
+/* ---- residual: R = L(S) - F of the five second-order forms -----------------------------------------------------
+ * The stop rule of a solve (flags[1], the relative change of mean|S| between two sweeps) does not say how well S satisfies
+ * the equation.  These entries do: a pure function of S -- nothing is swept, S and the coefficients are only read, no
+ * 'extend' pre-pass runs.  At every point the reference's kernel updates (rows / planes 1 .. n-2, columns 1 .. xc-2, and
+ * columns 0 and xc-1 when BCx is periodic, where its operand predicate holds) R is the reference's `temp` BEFORE the
+ * relaxation scaling, divided once by delxSqr: L(S) - F in the units of the forcing, with the reference's expression,
+ * association, periodic branches (and their irregularities) and no contraction.  Everywhere else R = undef.  R = 0 (to
+ * rounding) is the fixed point the sweeps converge to, in either ordering.  A NULL B (standard and general 2-D forms)
+ * means identically zero: the 5-point expression, B not tested.
+ * Arguments: R, S, then the form's arrays and scalars exactly as its solve entries take them (optArg is accepted and
+ * ignored; `...` below: the scalars from yc / zc up to the ratios).  strides[]: R, S, then the arrays, in elements
+ * between two members; 0 = one copy shared by every member (not R).  norms: host double[nbatch][4] = {n_live, mean|R|,
+ * max|R|, max|F|} over the member's live points (F: the form's forcing array), or NULL; reduced on the device in a fixed
+ * order without floating-point atomics, so two calls give the same bits.  A live NaN makes mean|R| and max|R| NaN; a
+ * member without a live point has mean|R| = NaN and both maxima 0.
+ * _dev: device pointers, the current device, queued on `stream`; with norms the call waits for them, without it returns
+ * before the launch has run.  _batched: host pointers (upload -- a shared array once --, one launch, download R: the plain
+ * staging of the side families), on opt->device; f32_mask, prep_flags, rowconst_mask and ndev > 1 are refused.
+ * XINV_ERR_ARG when R overlaps an input, for a null array (but B), a stride shorter than a slice, and for the shapes and
+ * codes the solve entries refuse (a core dimension < 3, an unknown BC code, nbatch < 1).
+ *   xinv_residual_standard_2d_f64_dev(R, S, A, B, C, F, nbatch, strides, ..., optArg, undef, norms, stream)
+ *   xinv_residual_standard_2d_f64_batched(R, S, A, B, C, F, nbatch, strides, ..., optArg, undef, norms, opt)
+ *   xinv_residual_general_2d_f64_dev(R, S, A, B, C, D, E, F, G, nbatch, strides, ..., optArg, undef, norms, stream)
+ *   xinv_residual_general_2d_f64_batched(R, S, A, B, C, D, E, F, G, nbatch, strides, ..., optArg, undef, norms, opt)
+ *   xinv_residual_standard_2d_test_f64_dev(R, S, A, B, C, D, E, F, nbatch, strides, ..., optArg, undef, norms, stream)
+ *   xinv_residual_standard_2d_test_f64_batched(R, S, A, B, C, D, E, F, nbatch, strides, ..., optArg, undef, norms, opt)
+ *   xinv_residual_standard_3d_f64_dev(R, S, A, B, C, F, nbatch, strides, ..., optArg, undef, norms, stream)
+ *   xinv_residual_standard_3d_f64_batched(R, S, A, B, C, F, nbatch, strides, ..., optArg, undef, norms, opt)
+ *   xinv_residual_general_3d_f64_dev(R, S, A, B, C, D, E, F, G, H, nbatch, strides, ..., optArg, undef, norms, stream)
+ *   xinv_residual_general_3d_f64_batched(R, S, A, B, C, D, E, F, G, H, nbatch, strides, ..., optArg, undef, norms, opt)
+ * Not covered: the biharmonic form and the 1-D form.  The prototypes live in a header of their own, which this one
+ * includes: a caller of xinv.h has them. */
+#include "xinv_resid.h"
+
 /* ---- resident plans: what a solve derives from the coefficient stack, built once -------------------------------
  * The reference calls its kernel again and again on ONE coefficient stack: apps.animate_iteration (apps.py:1031-1044:
  * `invt_func(*coeffs, maskF, initS, dims, iParams)` once per frame, tests/test_AnimateConverge.py:13-31: 40 frames of

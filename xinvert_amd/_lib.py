@@ -75,6 +75,11 @@ EXPORTS = [
     'xinv_tridiag_f64', 'xinv_tridiag_f64_dev',
     'xinv_fd_f64', 'xinv_fd_f64_dev',
     'xinv_mg_restrict_f64_dev', 'xinv_mg_prolong_f64_dev',
+    'xinv_residual_standard_2d_f64_dev', 'xinv_residual_standard_2d_f64_batched',
+    'xinv_residual_general_2d_f64_dev', 'xinv_residual_general_2d_f64_batched',
+    'xinv_residual_standard_2d_test_f64_dev', 'xinv_residual_standard_2d_test_f64_batched',
+    'xinv_residual_standard_3d_f64_dev', 'xinv_residual_standard_3d_f64_batched',
+    'xinv_residual_general_3d_f64_dev', 'xinv_residual_general_3d_f64_batched',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -109,6 +114,9 @@ def load():
     from . import forms
     for kind, f in forms.FORMS.items():
         for entry in ('single', 'batched', 'dev') + (('plan',) if f.resident else ()):
+            getattr(L, forms.symbol(kind, entry)).argtypes = forms.argtypes(kind, entry)
+    for kind in forms.RESIDUAL:
+        for entry in ('resid_dev', 'resid_batched'):
             getattr(L, forms.symbol(kind, entry)).argtypes = forms.argtypes(kind, entry)
     L.xinv_gm_flow_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _f64, _int, _vp]
     L.xinv_abs_norm_f64_dev.argtypes = [_vp, _i64, _f64, _dp, _vp]

@@ -295,6 +295,71 @@ def animate_iteration(app_name, F, dims, coords='lat-lon', icbc=None,
     return to_like(res, tmpl) if not isinstance(tmpl, Field) else res
 
 
+# the apps of the five second-order forms: app name -> (coefficient function name, core function name, valid mParams)
+_RESIDUAL = {k: v for k, v in _ANIMATE.items() if v[1] != 'inv_general2D_bih'}
+_RESIDUAL.update({
+    'gillmatsuno_test': ('_coeffs_GillMatsuno_test', 'inv_standard2D_test',
+                         ['f0', 'beta', 'epsilon', 'Phi', 'g', 'Omega', 'Rearth']),
+    'stommel_test': ('_coeffs_Stommel_test', 'inv_standard2D_test', ['beta', 'R', 'D', 'rho0', 'g', 'Omega', 'Rearth']),
+    'stommelarons': ('_coeffs_StommelArons', 'inv_general2D', ['f0', 'beta', 'epsilon', 'g', 'Omega', 'Rearth']),
+})
+
+
+def _res_func(inv_func):
+    """The res_* twin of a core.inv_* function (the five second-order forms), or None."""
+    return getattr(core, 'res_' + inv_func.__name__[len('inv_'):], None)
+
+
+def _solver_state(S_vals, maskF_vals, initS_vals):
+    """The state the solver left behind, out of the de-masked S a user holds: where the forcing is undefined the value
+    _mask_FS placed there (zero, or icbc) -- not the de-mask fill, which coast-adjacent points would otherwise read."""
+    return np.where(np.asarray(maskF_vals) == _undeftmp, np.asarray(initS_vals, dtype=np.float64),
+                    np.asarray(S_vals, dtype=np.float64))
+
+
+def _demask_residual(R, iParams):
+    return R.like(np.where(R.values != _undeftmp, R.values, iParams['undef']), 'residual')
+
+
+def residual(app_name, S, F, dims, coords='lat-lon', icbc=None,
+             mParams=default_mParams, iParams=default_iParams):
+    """R = L(S) - F of an `invert_*` result S for the forcing F it was computed from, in the units of the (scaled)
+    forcing the solver saw: the reference's point expression before the relaxation scaling, divided by delxSqr
+    (DESIGN.md 4.15).  Nothing is swept.  R holds iParams['undef'] where the solver updates nothing (boundaries, masked
+    points and their coefficient neighbours); iParams['resid'] = [nslice, 4] of {n_live, mean|R|, max|R|, max|F|}.
+    Apps of the five second-order forms; the biharmonic (StommelMunk) and 1-D apps raise."""
+    tmpl = F
+    F = from_any(F)
+    S = from_any(S, F.dims) if not isinstance(S, Field) else S
+    name = app_name.lower()
+    if name not in _RESIDUAL:
+        raise Exception('unsupported problem: ' + name + ', should be one of:\n' +
+                        '\n'.join(repr(k) for k in _RESIDUAL))
+    coef_name, inv_name, validMPs = _RESIDUAL[name]
+    coef_func, res_func = globals()[coef_name], _res_func(getattr(core, inv_name))
+    if len(F.dims) < len(dims) or tuple(S.shape) != tuple(F.shape):
+        raise Exception('S and F need the same shape, with the dims ' + repr(dims))
+    iParams_in = iParams
+    iParams = _update(default_iParams, iParams)
+    mParams = _update(default_mParams, mParams, validMPs)
+    if icbc is not None:
+        icbc = from_any(icbc)
+    maskF, initS, coeffs = coef_func(F, dims, coords, mParams, iParams, icbc)
+    if len(dims) == 2:
+        ps = _cal_params2D(maskF[dims[0]], maskF[dims[1]], coords, Rearth=mParams['Rearth'])
+    elif len(dims) == 3:
+        ps = _cal_params3D(maskF[dims[0]], maskF[dims[1]], maskF[dims[2]], coords, Rearth=mParams['Rearth'])
+    else:
+        raise Exception('dimension length should be one of [2, 3]')
+    iParams = _update(ps, iParams)
+    state = maskF.like(_solver_state(S.values, maskF.values, initS.values))
+    R = _demask_residual(res_func(*coeffs, maskF, state, dims, iParams), iParams)
+    if isinstance(iParams_in, dict) and iParams_in is not default_iParams:
+        iParams_in['resid'] = iParams['resid']
+    R.iParams = iParams
+    return to_like(R, tmpl) if not isinstance(tmpl, Field) else R
+
+
 def _deriv_center(vals, axis, coord, BC, scale=1.0, fill=0.0):
     """Centred first derivative with one padded point per side (reference finitediffs.py:548-659,
     `padBCs` + `deriv(scheme='center')`): pad by the boundary condition, extrapolate the
@@ -473,7 +538,13 @@ def _template(coef_func, inv_func, dimLen, F, dims, coords='lat-lon', icbc=None,
 
     # 1. coefficients (`_lazy`: builders that can may describe the forcing instead of computing it;
     #    iParams['device_prep'] = False keeps everything on the host, as the reference)
-    iParams['_lazy'] = True
+    #    iParams['residual'] = True: the residual is evaluated on the solver state below, which a lazy forcing never
+    #    brings to the host -- so the forcing is built here
+    want_resid = bool(iParams.get('residual')) and _res_func(inv_func) is not None
+    if iParams.get('residual') and not want_resid:
+        raise Exception("iParams['residual'] is available for the second-order 2-D and 3-D forms only, not for "
+                        + inv_func.__name__)
+    iParams['_lazy'] = not want_resid
     maskF, initS, coeffs = coef_func(F, dims, coords, mParams, iParams, icbc)
     iParams.pop('_lazy', None)
 
@@ -496,6 +567,8 @@ def _template(coef_func, inv_func, dimLen, F, dims, coords='lat-lon', icbc=None,
     # 3. invert (HIP kernels; in place on initS -- or, with a lazy forcing, from zeros on the device
     #    with the forcing masked / scaled and the output de-masked there too)
     S = inv_func(*coeffs, maskF, initS, dims, iParams)
+    if want_resid:                 # L(S) - F of the state the solver left, before the de-mask (iParams['resid'])
+        _res_func(inv_func)(*coeffs, maskF, S, dims, iParams)
 
     # 4. de-mask
     if iParams.pop('_demasked', False):

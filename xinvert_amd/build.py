@@ -58,6 +58,8 @@ UNITS = [
     ('xinv_tu_fd', 'xinv_tu_fd.hip', []),
     # multigrid grid transfers (invert_MultiGrid): k_mg_restrict, k_mg_prolong
     ('xinv_tu_mg', 'xinv_tu_mg.hip', []),
+    # the residual L(S) - F of the second-order forms: one streaming launch per call (k_resid2d, k_resid3d)
+    ('xinv_tu_resid', 'xinv_tu_resid.hip', []),
 ]
 # XINV_VARIANT_UNITS="xinv_tu_fused3d,..." (with XINV_BUILD_TAG): only these units are compiled with the extra flags; every
 # other object is taken from the shipped build's build/obj (a variant of one kernel family links in seconds)
@@ -83,8 +85,9 @@ def hipcc():
 
 
 def _abi_headers():
-    """include/xinv.h and the header it includes (xinv_trace.h: the tridiagonal solver's prototypes)."""
-    return [os.path.join(HERE, '..', 'include', f) for f in ('xinv.h', 'xinv_trace.h')]
+    """include/xinv.h and the headers it includes (xinv_trace.h: the tridiagonal solver's prototypes; xinv_resid.h: the
+    residual's)."""
+    return [os.path.join(HERE, '..', 'include', f) for f in ('xinv.h', 'xinv_trace.h', 'xinv_resid.h')]
 
 
 def _headers():

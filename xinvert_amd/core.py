@@ -77,6 +77,40 @@ def inv_general3D(A, B, C, D, E, F, G, H, S, dims, iParams):
     return _solve('gen3d', (A, B, C, D, E, F, G), H, S, dims, iParams)
 
 
+# ---- the residual L(S) - F of the five second-order forms (include/xinv_resid.h) -----------------------------------
+# Same arguments as the inv_* twin.  Nothing is swept and S is not modified: -> R as a Field shaped like F, `undef` (the
+# solver's internal -9.99e8) where the reference's kernel updates nothing; iParams['resid'] = [nbatch, 4] of
+# {n_live, mean|R|, max|R|, max|F|}.  The biharmonic and 1-D forms have no residual yet.
+def res_standard2D(A, B, C, F, S, dims, iParams):
+    if len(dims) != 2:
+        raise Exception('2 dimensions are needed for inversion')
+    return _residual('std2d', (A, B, C), F, S, dims, iParams)
+
+
+def res_standard2D_test(A, B, C, D, E, F, S, dims, iParams):
+    if len(dims) != 2:
+        raise Exception('2 dimensions are needed for inversion')
+    return _residual('std2dt', (A, B, C, D, E), F, S, dims, iParams)
+
+
+def res_general2D(A, B, C, D, E, F, G, S, dims, iParams):
+    if len(dims) != 2:
+        raise Exception('2 dimensions are needed for inversion')
+    return _residual('gen2d', (A, B, C, D, E, F), G, S, dims, iParams)
+
+
+def res_standard3D(A, B, C, F, S, dims, iParams):
+    if len(dims) != 3:
+        raise Exception('3 dimensions are needed for inversion')
+    return _residual('std3d', (A, B, C), F, S, dims, iParams)
+
+
+def res_general3D(A, B, C, D, E, F, G, H, S, dims, iParams):
+    if len(dims) != 3:
+        raise Exception('3 dimensions are needed for inversion')
+    return _residual('gen3d', (A, B, C, D, E, F, G), H, S, dims, iParams)
+
+
 # ------------------------------------------------------------------------------ internals
 def _vals(a):
     return a.values if isinstance(a, Field) or hasattr(a, 'values') else np.asarray(a)
@@ -341,6 +375,44 @@ def _result_empty(shape, dtype, iParams):
         except Exception:
             pass
     return np.empty(shape, dtype=dtype)
+
+
+def _residual(kind, coefs, F, S, dims, iParams):
+    """One call of xinv_residual_<form>_f64_batched on every slice (float64, full arrays: a coefficient that is one value
+    per row is expanded here)."""
+    if not isinstance(F, Field) or not isinstance(S, Field):
+        raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
+    perm, _, bshape = _batch_layout(F, dims)
+    core_shape = tuple(F.shape[F.axis(d)] for d in dims)
+    nbatch = int(np.prod(bshape)) if bshape else 1
+    n = int(np.prod(core_shape))
+    if nbatch == 0:
+        iParams['resid'] = np.zeros((0, 4))
+        return F.like(np.zeros(F.shape), 'residual')
+    L = _lib.require_gpu()
+    tr = lambda v: np.ascontiguousarray(np.transpose(np.asarray(v, dtype=np.float64), perm)).reshape((nbatch,) + core_shape)
+    Rv = np.empty((nbatch,) + core_shape)
+    arrs, strides = [Rv, tr(S.values)], [n, n]
+    for k, c in enumerate(coefs):
+        a, st, rc = _prep_coef(c, F, perm, core_shape, nbatch, allow_null=(k == 1 and forms.FORMS[kind].null_B))
+        if a is not None:
+            if rc:
+                a = np.broadcast_to(a[..., None], a.shape + (core_shape[-1],))
+                st = n if st else 0
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        arrs.append(a)
+        strides.append(st)
+    arrs.append(tr(F.values))
+    strides.append(n)
+    norms = np.zeros((nbatch, 4))
+    scal = forms.scalars(forms.from_iparams(kind, iParams, _undeftmp))
+    opt = _lib.options(device=int(iParams.get('device', -1)))
+    rc = getattr(L, forms.symbol(kind, 'resid_batched'))(*[_lib.hptr(a) for a in arrs], nbatch, _lib.strides_arg(strides),
+                                                         *scal, _lib.hptr(norms), opt)
+    _lib.check(rc)
+    iParams['resid'] = norms
+    out = np.transpose(Rv.reshape(tuple(bshape) + core_shape), np.argsort(perm))
+    return F.like(np.ascontiguousarray(out), 'residual')
 
 
 def _solve(kind, coefs, F, S, dims, iParams):

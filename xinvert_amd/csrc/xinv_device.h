@@ -569,3 +569,201 @@ __device__ __forceinline__ void bih_far(const Tri &t, double &cm4, double &cm3)
     cm3 = xinv_lane_up(t.v[0]);
 }
 
+
+// ---- point residuals: L(S) - F in the units of the forcing (k_resid2d / k_resid3d, xinv_resid.h) ----------------
+// The xinv_upd_* expression of the same form up to and including `temp` -- same operands, association and predicate --
+// and then temp / delxSqr where the update scales temp by optArg / denominator and adds it to S.  Returns the
+// reference's `cond`; r is written either way (the caller stores undef where cond is false).  optArg plays no part.
+
+// standard 2-D, 9-point (numbas.py:343-369; the i == 0 irregularity of 327-328 through bP_use / sM_q as in xinv_upd_std2d_9)
+__device__ __forceinline__ bool xinv_res_std2d_9(
+    double &r, double sC, double sP, double sM, double sW, double sE,
+    double sPE, double sPW, double sME, double sMW, double sM_q,
+    double aP, double a0, double bE, double bW, double bP_chk, double bP_use, double bM,
+    double cE, double c0, double f, const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (f != u) && (aP != u) && (a0 != u) && (bE != u) && (bW != u) &&
+                      (bP_chk != u) && (bM != u) && (cE != u) && (c0 != u);
+    double temp = (
+        (
+            aP * (sP - sC) -
+            a0 * (sC - sM)
+        ) * sc.ratioSqr + (
+            bP_use * (sPE - sPW) -
+            bM * (sM_q - sMW)
+        ) * sc.ratioQtr + (
+            bE * (sPE - sME) -
+            bW * (sPW - sMW)
+        ) * sc.ratioQtr + (
+            cE * (sE - sC) -
+            c0 * (sC - sW)
+        )
+    ) - f * sc.delxSqr;
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// standard 2-D with B NULL (identically 0): 5-point coupling, B is not tested
+__device__ __forceinline__ bool xinv_res_std2d_5(
+    double &r, double sC, double sP, double sM, double sW, double sE,
+    double aP, double a0, double cE, double c0, double f, const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (f != u) && (aP != u) && (a0 != u) && (cE != u) && (c0 != u);
+    double temp = (
+        (
+            aP * (sP - sC) -
+            a0 * (sC - sM)
+        ) * sc.ratioSqr + (
+            cE * (sE - sC) -
+            c0 * (sC - sW)
+        )
+    ) - f * sc.delxSqr;
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// general 2-D, 9-point (numbas.py:1125-1153)
+__device__ __forceinline__ bool xinv_res_gen2d_9(
+    double &r, double sC, double sP, double sM, double sW, double sE,
+    double sPE, double sPW, double sME, double sMW,
+    double A, double B, double C, double D, double E, double F, double G, const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (G != u) && (A != u) && (B != u) && (C != u) && (D != u) && (E != u) && (F != u);
+    double temp = (
+        A * (
+            (sP - sC) - (sC - sM)
+        ) * sc.ratioSqr +
+        B * (
+            (sPE - sME) - (sPW - sMW)
+        ) * sc.ratioQtr +
+        C * (
+            (sE - sC) - (sC - sW)
+        ) + (
+        D * (
+            (sP - sM)
+        ) * sc.ratio +
+        E * (
+            (sE - sW)
+        )) * sc.delx / 2.0 + (
+        F * sC - G) * sc.delxSqr
+    );
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// general 2-D with B NULL (identically 0)
+__device__ __forceinline__ bool xinv_res_gen2d_5(
+    double &r, double sC, double sP, double sM, double sW, double sE,
+    double A, double C, double D, double E, double F, double G, const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (G != u) && (A != u) && (C != u) && (D != u) && (E != u) && (F != u);
+    double temp = (
+        A * (
+            (sP - sC) - (sC - sM)
+        ) * sc.ratioSqr +
+        C * (
+            (sE - sC) - (sC - sW)
+        ) + (
+        D * (
+            (sP - sM)
+        ) * sc.ratio +
+        E * (
+            (sE - sW)
+        )) * sc.delx / 2.0 + (
+        F * sC - G) * sc.delxSqr
+    );
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// standard 2-D "test" form (numbas.py:563-589); B and C are always arrays here, so there is no 5-point case
+__device__ __forceinline__ bool xinv_res_std2dt_9(
+    double &r, double sC, double sP, double sM, double sW, double sE,
+    double sPE, double sPW, double sME, double sMW, double sM_q,
+    double aP, double a0, double bP_chk, double bP_use, double bM, double cE, double cW,
+    double dE, double d0, double e, double f, const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (f != u) && (aP != u) && (a0 != u) && (bP_chk != u) && (bM != u) &&
+                      (cE != u) && (cW != u) && (dE != u) && (d0 != u) && (e != u);
+    double temp = (
+        (
+            aP * (sP - sC) -
+            a0 * (sC - sM)
+        ) * sc.ratioSqr + (
+            bP_use * (sPE - sPW) -
+            bM * (sM_q - sMW)
+        ) * sc.ratioQtr + (
+            cE * (sPE - sME) -
+            cW * (sPW - sMW)
+        ) * sc.ratioQtr + (
+            dE * (sE - sC) -
+            d0 * (sC - sW)
+        )
+    ) + (e * sC - f) * sc.delxSqr;
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// standard 3-D, 7-point (numbas.py:146-169)
+__device__ __forceinline__ bool xinv_res_std3d(
+    double &r, double sC, double sKP, double sKM, double sJP, double sJM, double sE, double sW,
+    double aP, double a0, double bP, double b0, double cE, double c0, double f,
+    const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (f != u) && (aP != u) && (a0 != u) && (bP != u) && (b0 != u) &&
+                      (cE != u) && (c0 != u);
+    double temp = (
+        (
+            aP * (sKP - sC) -
+            a0 * (sC - sKM)
+        ) * sc.ratio2Sqr + (
+            bP * (sJP - sC) -
+            b0 * (sC - sJM)
+        ) * sc.ratio1Sqr + (
+            cE * (sE - sC) -
+            c0 * (sC - sW)
+        )
+    ) - f * sc.delxSqr;
+    r = temp / sc.delxSqr;
+    return cond;
+}
+
+// general 3-D, 7-point (numbas.py:899-930); testH false: the west-periodic branch, which never tests H (849-852)
+__device__ __forceinline__ bool xinv_res_gen3d(
+    double &r, double sC, double sKP, double sKM, double sJP, double sJM, double sE, double sW,
+    double A, double B, double C, double D, double E, double F, double G, double H, bool testH,
+    const XinvScal &sc)
+{
+    const double u = sc.undef;
+    const bool cond = (!testH || H != u) && (G != u) && (A != u) && (B != u) && (C != u) && (D != u) &&
+                      (E != u) && (F != u);
+    double temp = (
+        A * (
+            (sKP - sC)-(sC - sKM)
+        ) * sc.ratio2Sqr +
+        B * (
+            (sJP - sC)-(sC - sJM)
+        ) * sc.ratio1Sqr +
+        C * (
+            (sE - sC)-(sC - sW)
+        ) + (
+        D * (
+            (sKP - sKM)
+        ) * sc.ratio2 +
+        E * (
+            (sJP - sJM)
+        ) * sc.ratio1 +
+        F * (
+            (sE - sW)
+        )) * sc.delx / 2.0 + (
+        G * sC - H) * sc.delxSqr
+    );
+    r = temp / sc.delxSqr;
+    return cond;
+}

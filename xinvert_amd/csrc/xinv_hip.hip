@@ -73,6 +73,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_tridiag_host.h" /* trace / traceCyclic and the direct 1-D solve (k_tridiag) */
 #include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
 #include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
+#include "xinv_resid_host.h"   /* the residual L(S) - F of the second-order forms (k_resid2d, k_resid3d) */
 
 // ------------------------------------------------------------------ C-ABI
 extern "C" {
@@ -512,6 +513,154 @@ int xinv_tridiag_f64_dev(double *x, const double *a, const double *b, const doub
                          const double *cn, int64_t nbatch, const int64_t *strides, int64_t n, void *stream)
 {
     GUARD(tridiag_solve_dev(mk_tridiag(x, a, b, c, d, a0, cn, nbatch, strides, n), strides, (hipStream_t)stream))
+}
+
+// ---- the residual L(S) - F of the five second-order forms (k_resid2d / k_resid3d; include/xinv_resid.h) ------------
+// The solve entries' arrays and scalars behind R and S; optArg is accepted and ignored.
+int xinv_residual_standard_2d_f64_dev(double *R, const double *S, const double *A, const double *B, const double *C,
+                                      const double *F, int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc,
+                                      double dely, double delx, int BCy, int BCx, double delxSqr, double ratioQtr,
+                                      double ratioSqr, double optArg, double undef, double *norms, void *stream)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD2D, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_dev(rc_, strides, norms, (hipStream_t)stream))
+}
+
+int xinv_residual_standard_2d_f64_batched(double *R, const double *S, const double *A, const double *B,
+                                          const double *C, const double *F, int64_t nbatch, const int64_t *strides,
+                                          int64_t yc, int64_t xc, double dely, double delx, int BCy, int BCx,
+                                          double delxSqr, double ratioQtr, double ratioSqr, double optArg,
+                                          double undef, double *norms, const xinv_options *opt)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD2D, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_host(rc_, strides, norms, opt))
+}
+
+int xinv_residual_general_2d_f64_dev(double *R, const double *S, const double *A, const double *B, const double *C,
+                                     const double *D, const double *E, const double *F, const double *G,
+                                     int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc, double dely,
+                                     double delx, int BCy, int BCx, double delxSqr, double ratio, double ratioQtr,
+                                     double ratioSqr, double optArg, double undef, double *norms, void *stream)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_GEN2D, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_dev(rc_, strides, norms, (hipStream_t)stream))
+}
+
+int xinv_residual_general_2d_f64_batched(double *R, const double *S, const double *A, const double *B,
+                                         const double *C, const double *D, const double *E, const double *F,
+                                         const double *G, int64_t nbatch, const int64_t *strides, int64_t yc,
+                                         int64_t xc, double dely, double delx, int BCy, int BCx, double delxSqr,
+                                         double ratio, double ratioQtr, double ratioSqr, double optArg, double undef,
+                                         double *norms, const xinv_options *opt)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F, G };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio = ratio; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_GEN2D, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_host(rc_, strides, norms, opt))
+}
+
+int xinv_residual_standard_2d_test_f64_dev(double *R, const double *S, const double *A, const double *B,
+                                           const double *C, const double *D, const double *E, const double *F,
+                                           int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc,
+                                           double dely, double delx, int BCy, int BCx, double delxSqr,
+                                           double ratioQtr, double ratioSqr, double optArg, double undef,
+                                           double *norms, void *stream)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD2DT, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_dev(rc_, strides, norms, (hipStream_t)stream))
+}
+
+int xinv_residual_standard_2d_test_f64_batched(double *R, const double *S, const double *A, const double *B,
+                                               const double *C, const double *D, const double *E, const double *F,
+                                               int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc,
+                                               double dely, double delx, int BCy, int BCx, double delxSqr,
+                                               double ratioQtr, double ratioSqr, double optArg, double undef,
+                                               double *norms, const xinv_options *opt)
+{
+    (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratioQtr = ratioQtr; sc.ratioSqr = ratioSqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD2DT, R, S, c, nbatch, strides, 1, yc, xc, 0, BCy, BCx, sc);
+    GUARD(resid_host(rc_, strides, norms, opt))
+}
+
+int xinv_residual_standard_3d_f64_dev(double *R, const double *S, const double *A, const double *B, const double *C,
+                                      const double *F, int64_t nbatch, const int64_t *strides, int64_t zc, int64_t yc,
+                                      int64_t xc, double delz, double dely, double delx, int BCz, int BCy, int BCx,
+                                      double delxSqr, double ratio2Sqr, double ratio1Sqr, double optArg, double undef,
+                                      double *norms, void *stream)
+{
+    (void)delz; (void)dely; (void)delx; (void)optArg;
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD3D, R, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc);
+    GUARD(resid_dev(rc_, strides, norms, (hipStream_t)stream))
+}
+
+int xinv_residual_standard_3d_f64_batched(double *R, const double *S, const double *A, const double *B,
+                                          const double *C, const double *F, int64_t nbatch, const int64_t *strides,
+                                          int64_t zc, int64_t yc, int64_t xc, double delz, double dely, double delx,
+                                          int BCz, int BCy, int BCx, double delxSqr, double ratio2Sqr,
+                                          double ratio1Sqr, double optArg, double undef, double *norms,
+                                          const xinv_options *opt)
+{
+    (void)delz; (void)dely; (void)delx; (void)optArg;
+    const double *c[] = { A, B, C, F };
+    XinvScal sc = {};
+    sc.delxSqr = delxSqr; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_STD3D, R, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc);
+    GUARD(resid_host(rc_, strides, norms, opt))
+}
+
+int xinv_residual_general_3d_f64_dev(double *R, const double *S, const double *A, const double *B, const double *C,
+                                     const double *D, const double *E, const double *F, const double *G,
+                                     const double *H, int64_t nbatch, const int64_t *strides, int64_t zc, int64_t yc,
+                                     int64_t xc, double delz, double dely, double delx, int BCz, int BCy, int BCx,
+                                     double delxSqr, double ratio2, double ratio1, double ratio2Sqr, double ratio1Sqr,
+                                     double optArg, double undef, double *norms, void *stream)
+{
+    (void)delz; (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_GEN3D, R, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc);
+    GUARD(resid_dev(rc_, strides, norms, (hipStream_t)stream))
+}
+
+int xinv_residual_general_3d_f64_batched(double *R, const double *S, const double *A, const double *B,
+                                         const double *C, const double *D, const double *E, const double *F,
+                                         const double *G, const double *H, int64_t nbatch, const int64_t *strides,
+                                         int64_t zc, int64_t yc, int64_t xc, double delz, double dely, double delx,
+                                         int BCz, int BCy, int BCx, double delxSqr, double ratio2, double ratio1,
+                                         double ratio2Sqr, double ratio1Sqr, double optArg, double undef,
+                                         double *norms, const xinv_options *opt)
+{
+    (void)delz; (void)dely; (void)optArg;
+    const double *c[] = { A, B, C, D, E, F, G, H };
+    XinvScal sc = {};
+    sc.delx = delx; sc.delxSqr = delxSqr; sc.ratio2 = ratio2; sc.ratio1 = ratio1; sc.ratio2Sqr = ratio2Sqr; sc.ratio1Sqr = ratio1Sqr; sc.undef = undef;
+    const ResidCall rc_ = mk_resid(KIND_GEN3D, R, S, c, nbatch, strides, zc, yc, xc, BCz, BCy, BCx, sc);
+    GUARD(resid_host(rc_, strides, norms, opt))
 }
 
 // ---- finite differences (k_fd) ----------------------------------------------------------------------------------

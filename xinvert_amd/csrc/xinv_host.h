@@ -337,6 +337,7 @@ struct Workspace {
     int *h_tri_ovf = nullptr; size_t h_tri_ovf_cap = 0;         // ... and their pinned mirror
     Behind tri_user;                                            // xinv_tridiag_f64_dev only queues its kernel, which reads and
                                                                 // writes `tri` until it ends: the next user of `tri` waits on it
+    double *res_part = nullptr; size_t res_part_cap = 0;        // k_resid*: norm partials [nbatch][slots][4], then the norms [nbatch][4]
     StageRing ring_up, ring_down;                               // host-pointer entries: the library's pinned staging
 };
 

@@ -5,6 +5,9 @@ Every form has up to four entry points: 'single' (one slice, host pointers), 'ba
 pointers) and 'plan' (xinv_plan_create_*_dev).  Their parameters are, in order: S (plan: the handle's address), the
 coefficient arrays with the forcing last, `nbatch, strides` (not single), the form's scalars, `flags, mxLoop, tolerance`
 (not plan), `opt` (not single, except the 1-D form), `stream` (dev, plan).  tests/test_host.py holds the table to the header.
+
+The five second-order forms (RESIDUAL) also have 'resid_dev' and 'resid_batched' (include/xinv_resid.h): `R, S`, the arrays,
+`nbatch, strides`, the same scalars, `norms`, then `stream` / `opt`.
 """
 import ctypes
 from collections import namedtuple
@@ -36,6 +39,9 @@ FORMS = {f.kind: f for f in (
     _form('std1d', 'standard_1d', 'inv_standard1D', 1, 'ABF', 'xc delx BCx delxSqr', resident=False, single_opt=True),
 )}
 
+# the forms xinv_residual_* exists for, in the order of include/xinv_resid.h
+RESIDUAL = ('std2d', 'gen2d', 'std2dt', 'std3d', 'gen3d')
+
 # a scalar's iParams key where it is not the scalar's own name (BC codes: iParams['BCs'] by position; undef: the caller's)
 IPARAM = {'xc': 'gc1', 'yc': 'gc2', 'zc': 'gc3', 'delx': 'del1', 'dely': 'del2', 'delz': 'del3',
           'delxSqr': 'del1Sqr', 'delxSSr': 'del1SSr', 'delxTr': 'del1Tr'}
@@ -53,7 +59,10 @@ def symbol(kind, entry):
     f = FORMS[kind]
     if entry == 'plan' and not f.resident:
         raise KeyError('the %s form has no plan entry' % kind)
-    return {'single': 'xinv_%s_f64', 'batched': 'xinv_%s_f64_batched', 'dev': 'xinv_%s_f64_dev',
+    if entry.startswith('resid_') and kind not in RESIDUAL:
+        raise KeyError('the %s form has no residual entry' % kind)
+    return {'resid_dev': 'xinv_residual_%s_f64_dev', 'resid_batched': 'xinv_residual_%s_f64_batched',
+            'single': 'xinv_%s_f64', 'batched': 'xinv_%s_f64_batched', 'dev': 'xinv_%s_f64_dev',
             'plan': 'xinv_plan_create_%s_f64_dev'}[entry] % f.name
 
 
@@ -62,12 +71,16 @@ def params(kind, entry):
     entries as addresses (integers); `flags` is a host array everywhere."""
     f = FORMS[kind]
     symbol(kind, entry)                                  # (raises for an entry the form does not have)
-    arr =_dp if entry in ('single', 'batched') else _vp
+    arr =_dp if entry in ('single', 'batched', 'resid_batched') else _vp
     ps = [('plan', ctypes.POINTER(_vp))] if entry == 'plan' else [('S', arr)]
+    if entry.startswith('resid_'):
+        ps.insert(0, ('R', arr))
     ps += [(a, arr) for a in f.arrays]
     if entry != 'single':
         ps += [('nbatch', _i64), ('strides', _ip)]
     ps += [(s, _ctype(s)) for s in f.scalars]
+    if entry.startswith('resid_'):
+        return ps + [('norms', _dp), ('stream', _vp) if entry == 'resid_dev' else ('opt', _opt)]
     if entry != 'plan':
         ps += [('flags', _dp), ('mxLoop', _i64), ('tolerance', _f64)]
     if entry != 'single' or f.single_opt:

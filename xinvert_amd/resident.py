@@ -188,6 +188,44 @@ class ResidentProblem:
         self.flags[:] = fl[-1]
         return fl, _lib.last_stats()
 
+    def full_arrays(self):
+        """The coefficient stack as the entries that take full arrays want it -> (arrays, strides of S and the arrays):
+        a coefficient kept as one value per row is expanded along x (a fresh tensor on the current stream)."""
+        cs, strides = [], [self.n]
+        for k, c in enumerate(self.coefs):
+            if c is not None and (self.rowconst >> k) & 1:
+                c = c.unsqueeze(-1).expand(*c.shape, self.core[-1]).contiguous()
+                strides.append(self.n if self._strides[1 + k] else 0)
+            else:
+                strides.append(self._strides[1 + k])
+            cs.append(c)
+        return cs, strides
+
+    def residual(self, stream=None):
+        """R = L(S) - F of the resident state, on the device (include/xinv_resid.h; S is not modified) -> (R as a torch
+        tensor shaped like S, norms [nb, 4] = {n_live, mean|R|, max|R|, max|F|}).  Coefficients kept as one value per row
+        are expanded for the call."""
+        import torch
+        if self.kind not in forms.RESIDUAL:
+            raise _lib.XinvError('the %s form has no residual entry' % self.kind)
+        cur = torch.cuda.current_stream(self.dev)
+        st = stream if stream is not None else cur
+        self._join()
+        # R and the expanded coefficients belong to the current stream, which is where the caller goes on using R; the
+        # call's stream waits for them, and the call returns only after its launch has run (it brings the norms back)
+        R = torch.empty_like(self.S)
+        cs, strides = self.full_arrays()
+        if st.cuda_stream != cur.cuda_stream:
+            st.wait_stream(cur)
+        norms = np.zeros((self.nb, 4))
+        rc = getattr(self.L, forms.symbol(self.kind, 'resid_dev'))(
+            _lib.dptr(R), _lib.dptr(self.S), *[_lib.dptr(c) for c in cs], self.nb, _lib.strides_arg([self.n] + strides),
+            *scalars(self.p), _lib.hptr(norms), ctypes.c_void_p(st.cuda_stream))
+        _lib.check(rc)
+        if st.cuda_stream != cur.cuda_stream:
+            cur.wait_stream(st)
+        return R, norms
+
     def result(self):
         self._join()
         return self.S.cpu().numpy()
