@@ -505,7 +505,8 @@ static int launch_colour_sweep(const Problem &p, const Plan &pl, Workspace *ws, 
 
 // The tiling cost model of the fused 2-D kernels -- xinv_tile_cost, and xinv_choose_row_blocks which minimises it: xinv_tiles.h,
 // checked on the CPU -- with the kernels' constants: at most three workgroups of k_fused2d / k_fused9 per CU count; of the
-// pipelined kernel up to XINV_PIPE_OCC workgroups -- one wavefront each per SIMD -- share a CU.
+// pipelined kernel up to XINV_PIPE_OCC workgroups -- one wavefront each per SIMD -- share a CU.  For the pipelined pass
+// `rows` is the height of the split's TALLEST tile (tallest_tile below): its steps are the kernel's own count.
 static int pipe_occ_cap()
 {
     return std::max(1, XINV_ENV_INT("XINV_PIPE_OCC", 5));
@@ -513,12 +514,14 @@ static int pipe_occ_cap()
 
 static double tile_cost(int64_t wgs, int64_t rows, int K, int occ, double lone, bool pipe)
 {
-    return xinv_tile_cost(wgs, rows, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0);
+    return xinv_tile_cost(wgs, rows, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0, pipe ? XINV_PIPE_B : 0,
+                          XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4);
 }
 
 static int64_t choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int K, int occ, double lone, bool pipe)
 {
-    return xinv_choose_row_blocks(yc, nstrip, nbatch, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0);
+    return xinv_choose_row_blocks(yc, nstrip, nbatch, K, occ, pipe ? pipe_occ_cap() : 3, lone, pipe ? XINV_PIPE_LAG : 0,
+                                  pipe ? XINV_PIPE_B : 0, XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4);
 }
 
 // How many workgroups of the planned kernel variant fit on a CU at K sweeps per pass (register-limited: asked of the
@@ -667,7 +670,12 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
     };
     const int occ = fixedRB ? 2 : plan_occ(p, pl, st, K);
     const bool pp = pl.pipe;
-    const double cost0 = tile_cost((int64_t)cdiv((int64_t)nstrip * pl.nrb, tpw) * nb, cdiv(yc, pl.nrb), K, occ, pl.lone, pp);
+    // the rows tile_cost is handed for a split into nrb blocks: the pipelined pass is costed by its tallest tile
+    auto cost_rows = [&](int nrb) -> int64_t {
+        if (!pp) return cdiv(yc, nrb);
+        return pl.even_split ? xinv_even_split_tallest(yc, nrb) : std::min<int64_t>(pl.RY, yc);
+    };
+    const double cost0 = tile_cost((int64_t)cdiv((int64_t)nstrip * pl.nrb, tpw) * nb, cost_rows(pl.nrb), K, occ, pl.lone, pp);
     // candidates: the row split that brings the ACTIVE workgroups back to the default count sits
     // near nrb / (active share); search a window around it
     int best = pl.nrb; double best_cost = 1e300;
@@ -680,9 +688,9 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
         lo = (int)std::min<int64_t>(cap_rows, std::max<int64_t>(pl.nrb, (int64_t)(centre * 0.85)));
         hi = (int)std::min<int64_t>(cap_rows, std::max<int64_t>(lo, (int64_t)(centre * 1.10) + 1));
     }
-    best_cost = tile_cost(active_wgs(pl.nrb, nullptr), cdiv(yc, pl.nrb), K, occ, pl.lone, pp);   // keep the split, skip only
+    best_cost = tile_cost(active_wgs(pl.nrb, nullptr), cost_rows(pl.nrb), K, occ, pl.lone, pp);   // keep the split, skip only
     for (int nrb = lo; nrb <= hi; nrb++) {
-        const double c = tile_cost(active_wgs(nrb, nullptr), cdiv(yc, nrb), K, occ, pl.lone, pp);
+        const double c = tile_cost(active_wgs(nrb, nullptr), cost_rows(nrb), K, occ, pl.lone, pp);
         if (c < best_cost) { best_cost = c; best = nrb; }
     }
     if (!forced && best_cost > 0.95 * cost0) return XINV_OK;            // (fixed split: skipping must save 5 % of the workgroups)

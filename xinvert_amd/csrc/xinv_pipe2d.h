@@ -16,10 +16,31 @@
 // Schedule.  With r the row that enters wavefront p's four-row register window at a step, the wavefront
 // updates its red points on row r-1 and its black points on row r-2 (sweep p+1), and row r-2 leaves: into
 // the ring (p < 3) or to HBM (p = 3, owned rows only).  Wavefront p+1 asks for that row one step later and
-// enters it the step after (LDS latency hidden behind a step of arithmetic), so it runs LAG = 6 steps
-// behind wavefront p.  One `s_waitcnt lgkmcnt(0); s_barrier` per step keeps the four in step (no vmcnt
+// enters it the step after (LDS latency hidden behind a step of arithmetic), so it runs LAG = B + 5 steps
+// behind wavefront p.  One `s_waitcnt lgkmcnt(0); s_barrier` every B steps keeps the four in step (no vmcnt
 // wait: the global prefetch of wavefront 0 stays in flight across barriers).  Wavefront 0 reads S and every
 // wavefront reads the forcing rows it needs from global memory (the later ones hit in L2) PF rows ahead.
+//
+// Who marches which rows in which global step is defined ONCE, in xinv_tiles.h (xinv_pipe_*): this kernel, the
+// planner's step count and the CPU simulation of the ring hand-over (tests/test_pipe_schedule.py) call the same
+// functions.  A march is whole unroll periods of R = 8 rows, so a wavefront that needs n rows marches up to 7 more.
+// The launch ends when the LAST wavefront of the tallest tile ends, so padding behind that wavefront's last row is
+// time nothing needs (six steps of 78 on 46-row tiles, the headline's).  Wavefronts 1..3 therefore pad in FRONT:
+// they start `front` steps early (even, as much of the padding as fits), on rows above the first one they need,
+// while the pipeline fills and their SIMD is idle, and keep at most one padded row at the end.  Wavefront 0 cannot
+// start before step 0 and always finishes first: its padding stays at the end.
+// Why the front rows are harmless.  They are full steps on whatever the loads (clamped to the slice) and the ring
+// (stale LDS) deliver.  A wavefront's red update of row j reads rows j-1, j, j+1 of its input and its black update
+// of row j the red values of rows j-1 and j+1, so its output is valid from two rows below its first valid input row:
+// wavefront p's first needed row is in_lo = yu0 - 8 + 2p, nothing it keeps -- rows >= in_lo + 2 for the next
+// wavefront, owned rows for the norm and the stores -- reads a row above in_lo.  Before the front padding those rows
+// of the window were zeros, and equally unread.  The ring reads of needed rows and the writes they wait for sit in
+// the same global steps as without padding; the padded writes come before them, into slots whose needed rows are
+// written later, and the norm share and the stores are guarded by "owned row".  The 'extend' pre-pass (EXT: row 1
+// copied into row 0, row yc-2 into row yc-1, when row 1 / yc-2 is the red row of a step) can now fire on a padded
+// step of a tile that is not at the top -- 12 owned rows from row 12 on, wavefront 1, six rows in front: the march
+// starts at row 0 -- and then copies stale LDS data (through xinv_lane_up as well) between two window rows above
+// in_lo: rows of the same unread kind.
 //
 // The relaxation factor optArg / ((A[j+1] + A[j]) ratioSqr + 2 C[j]) is uniform along a row and the same
 // for every sweep of the solve: k_row_factor evaluates it once per solve (same expression, same bits) with
@@ -255,8 +276,21 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     static_assert(!SEAM || (NP == 1 && !AL && PipeRec<M, UM>::HOIST),
                   "seam variants: one column pair per lane, per-row records, updates under EXEC masks");
 
-    const int in_lo = yu0 - H + 2 * PW;                  // first / last row entering this wavefront's window
+    // the schedule (xinv_tiles.h): the first row marched -- `front` padded rows above the first one needed -- and the last
+    // row needed; the march runs whole periods from the one past the other
+    const int front = xinv_pipe_front(yu1 - yu0, PW, LAG, R);
+    const int in_lo = yu0 + xinv_pipe_first_row(yu1 - yu0, PW, LAG, R);
     const int in_hi = yu1 - 1 + H - 2 * PW;
+    // the LDS ring slot of a row is named at compile time from its position in this march; with front = 2 (mod 4) that
+    // name is two off the slot the neighbours know the row by: two base addresses inside the ring, one for the names 0 / 1
+    // (slot `flip`) and one for 2 / 3 (slot 2 - flip), indexed with the name's low bit, undo it (bit 1 of the name flipped;
+    // no instruction in the march: the slot stays an immediate offset of the ds instruction, below its 16 bits)
+    typedef double2 (*ring_t)[XINV_PIPE_NS][NP * (FR ? 2 : 1)][XINV_WAVE];
+    static_assert(XINV_PIPE_NS == 4 && (XINV_PIPE_P - 1) * sizeof(ring[0]) <= 65536, "ring offsets as ds immediates");
+    const int flip = PW > 0 ? xinv_pipe_slot_flip(front) : 0;
+    const ring_t ring_lo = (ring_t)(&ring[0][flip]);
+    const ring_t ring_hi = (ring_t)(&ring[0][2 - flip]);
+#define RING(pw_, name_) ((name_) < 2 ? ring_lo : ring_hi)[pw_][(name_) & 1]
 
     double2 sw[NP][R];
     CoefWin<NC, R> cw[NP];
@@ -278,8 +312,8 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     // the slice); the rows of a tile at the top or bottom of the slice are clamped to [0, yc-1] as before (their
     // updates are switched off by the row predicate).  Three scalar instructions per step for all streams.
     const int maxo = (int)(rowbytes * (unsigned)(ycr - 1));
-    int nxo = (yu0 - H + 2 * PW) * (int)rowbytes;
-    int nxr = (yu0 - H + 2 * PW) * (RW * 8);             // the same for the per-row records
+    int nxo = in_lo * (int)rowbytes;
+    int nxr = in_lo * (RW * 8);                          // the same for the per-row records
     // a row of one of the lane's column pairs
     auto ldrow = [&](__amdgpu_buffer_rsrc_t rs, int soff, auto qtag) {
         constexpr int q = decltype(qtag)::value;
@@ -381,8 +415,9 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
         }
     };
 
-    // global step g of the workgroup = local step + LAG * PW; a barrier closes every B-th global step.
-    // Row in_lo is taken out of the ring in global step LAG * PW - 1 -- the step before this wavefront's first,
+    // global step g of the workgroup = local step + LAG * PW - front (even: the barriers of the march stay compile-time);
+    // a barrier closes every B-th global step.
+    // Row in_lo is taken out of the ring in global step LAG * PW - front - 1 -- the step before this wavefront's first,
     // like every later row (one step before it enters) -- and BEFORE the barrier that may close that step: the
     // producer wrote it two steps earlier and reuses the slot two steps later, so the read has to sit in the
     // barrier interval between.  (Read after the pre-loop, as this code did until round 3, it fell into the
@@ -390,17 +425,19 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     // load the third wavefront sometimes got row in_lo + 4 for row in_lo, and the one point of the tile whose
     // dependency cone touches it, the first owned row's last half-sweep, came out wrong by a few ulps to 1e-4.
     // Found on 64 x 1440 x 720 Gill-Matsuno members; profiles/r03_pipe2d_ring_race.txt.)
+    // (With front > 0 row in_lo is padding and the read may be of a slot nobody has written yet; a wavefront that starts in
+    // step 0 skips it.)
+    const int gread = xinv_pipe_first_read(yu1 - yu0, PW, LAG, R);
     int g = 0;
+    for (; g < gread; g++) if ((g + 1) % B == 0) xinv_pipe_barrier();
+    if (PW > 0 && gread >= 0) {
 #pragma unroll
-    for (; g < LAG * PW; g++) {
-        if (PW > 0 && g == LAG * PW - 1) {
-#pragma unroll
-            for (int q = 0; q < NP; q++) {
-                sw[q][0] = ring[PW - 1][(2 * PW) % XINV_PIPE_NS][q * RS][lane];      // row in_lo
-                if (FR) cw[q].v[FQ][0] = ring[PW - 1][(2 * PW) % XINV_PIPE_NS][q * RS + 1][lane];
-            }
+        for (int q = 0; q < NP; q++) {
+            sw[q][0] = RING(PW - 1, (2 * PW) % XINV_PIPE_NS)[q * RS][lane];      // row in_lo
+            if (FR) cw[q].v[FQ][0] = RING(PW - 1, (2 * PW) % XINV_PIPE_NS)[q * RS + 1][lane];
         }
         if ((g + 1) % B == 0) xinv_pipe_barrier();
+        g++;
     }
 
     for (int rb_ = in_lo; rb_ <= in_hi; rb_ += R) {
@@ -408,7 +445,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
             constexpr int U = decltype(utag)::value;     // record of the entering row r
             constexpr int X = (U & 1) ? 0 : 1;
 #define SLOT(w) ((U - (w) + 4 * R) % R)
-#define RSLOT(w) ((2 * PW + U - (w) + 64 * XINV_PIPE_NS) % XINV_PIPE_NS)  /* LDS ring slot of row r - w */
+#define RSLOT(w) ((2 * PW + U - (w) + 64 * XINV_PIPE_NS) % XINV_PIPE_NS)  /* name of the LDS ring slot of row r - w */
 #define ITAG(v) std::integral_constant<int, (v)>{}
             const int r = rb_ + U;
             request(r + PF, ITAG((U + PF) % R));
@@ -416,8 +453,8 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
             if (PW > 0) {
 #pragma unroll
                 for (int q = 0; q < NP; q++) {
-                    sw[q][(U + 1) % R] = ring[PW - 1][RSLOT(-1)][q * RS][lane];   // row r+1: written B+1 steps ago
-                    if (FR) cw[q].v[FQ][(U + 1) % R] = ring[PW - 1][RSLOT(-1)][q * RS + 1][lane];
+                    sw[q][(U + 1) % R] = RING(PW - 1, RSLOT(-1))[q * RS][lane];   // row r+1: written B+1 steps ago
+                    if (FR) cw[q].v[FQ][(U + 1) % R] = RING(PW - 1, RSLOT(-1))[q * RS + 1][lane];
                 }
             }
             if constexpr (!HOIST) {          // coefficient arrays that vary along x: the model's own predicate
@@ -459,8 +496,8 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
                 if (PW < P - 1) {
 #pragma unroll
                     for (int q = 0; q < NP; q++) {
-                        ring[PW][RSLOT(2)][q * RS][lane] = sw[q][sj];
-                        if (FR) ring[PW][RSLOT(2)][q * RS + 1][lane] = cw[q].v[FQ][sj];
+                        RING(PW, RSLOT(2))[q * RS][lane] = sw[q][sj];
+                        if (FR) RING(PW, RSLOT(2))[q * RS + 1][lane] = cw[q].v[FQ][sj];
                     }
                 } else if ((unsigned)(jb - yu0) < (unsigned)(yu1 - yu0)) {
                     const int doff = jb * (int)rowbytes;
@@ -482,7 +519,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
                     }, std::make_integer_sequence<int, NP>{});
                 }
             }
-            if ((LAG * PW + U + 1) % B == 0) xinv_pipe_barrier();
+            if ((LAG * PW + U + 1) % B == 0) xinv_pipe_barrier();      // (front is even)
 #undef SLOT
 #undef RSLOT
 #undef ITAG
@@ -490,6 +527,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
         g += R;
     }
     for (; g < gtot; g++) if ((g + 1) % B == 0) xinv_pipe_barrier();
+#undef RING
 #pragma unroll
     for (int q = 0; q < NP; q++) {                       // only the columns this lane owns count
         acc += (lc[q].use_x ? nsx[q] : 0.0);
@@ -563,16 +601,7 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
 
     if (active) {
         // global steps every wavefront goes through: the longest of the four schedules, whole barrier periods
-        const int ry = yu1 - yu0;
-        int gtot = 0;
-#pragma unroll
-        for (int pw = 0; pw < P; pw++) {
-            const int per = (pw == 0 ? XINV_PIPE_PF0 : XINV_PIPE_PF) + 4;      // unroll period of that wavefront
-            const int n = ry + 2 * H - 4 * pw;
-            const int g = LAG * pw + ((n + per - 1) / per) * per;
-            gtot = g > gtot ? g : gtot;
-        }
-        gtot = ((gtot + B - 1) / B) * B;
+        const int gtot = xinv_pipe_gtot(yu1 - yu0, LAG, B, XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4);
         // SEAM: only the tiles that hold a seam lane take the march with the extra pass; every other tile of the launch
         // runs the plain one.  (One march with the extra passes behind wave-uniform branches cost EVERY tile its
         // instruction interleaving: 3601 columns ran 1.45x the time of 3600 -- profiles/r05_seam_rates.txt.)

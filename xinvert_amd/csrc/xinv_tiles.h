@@ -166,8 +166,83 @@ __host__ __device__ inline int xinv_p3_extend_joff(int64_t yc, int RJ, int H, in
     return xinv_p3_extend_ok(yc, 0, RJ, H, RR) ? 0 : (xinv_p3_extend_ok(yc, 2, RJ, H, RR) ? 2 : -1);
 }
 
+// ---- k_pipe2d (xinv_pipe2d.h): the schedule of the wave-pipelined pass ----------------------------------------------------
+// The ONE definition of who marches which rows at which global step of the workgroup: the kernel, the planner's step count
+// and the CPU simulation (tests/csrc/pipe_schedule_check.cpp) all call these.  Four wavefronts, wavefront pw applies sweep
+// pw + 1 to a tile of ry owned rows [yu0, yu0 + ry); rows are relative to yu0, `lag` = steps wavefront pw + 1 runs behind
+// wavefront pw, a barrier closes every b-th global step (step g is in barrier interval g / b), `period` = the unroll
+// period of that wavefront's march (a march is whole periods).
+//   needed rows     wavefront pw must enter the n = ry + 16 - 4 pw rows [-8 + 2 pw, ry + 7 - 2 pw], the first of them in
+//                   global step lag * pw (a row enters wavefront pw + 1 `lag` steps after it entered wavefront pw);
+//   padding         the march is rounded up to whole periods: pad = -n mod period extra rows.  Wavefront 0 cannot start
+//                   before step 0 and is never the last to finish: its padding stays at the end.  Wavefronts 1..3 start
+//                   EARLIER instead, in the pipeline's fill where their SIMD has nothing else to do: `front` rows above
+//                   the first needed one -- the largest even count (the colour of a row is compile-time in the unrolled
+//                   march) that the padding and the start allow -- and only pad - front <= 1 rows stay behind the last;
+//   ring slots      a wavefront names the LDS ring slot of a row at compile time from the row's position in ITS march,
+//                   (row - first row + 2 pw) mod 4, which is (row + 8 + front) mod 4: a wavefront whose front padding is
+//                   2 mod 4 flips bit 1 of the slot (xinv_pipe_slot_flip; a second base address, no instruction), and
+//                   every wavefront then finds row r in slot (r + 8) mod 4 whatever the others' padding.
+// A padded step is a full step -- loads (clamped to the slice), ring read, two half-sweeps, ring write, barrier -- on rows
+// nothing kept depends on (xinv_pipe2d.h: the header comment has the argument).
+__host__ __device__ inline int xinv_pipe_rows(int ry, int pw) { return ry + 16 - 4 * pw; }
+__host__ __device__ inline int xinv_pipe_pad(int ry, int pw, int period)
+{
+    return (period - xinv_pipe_rows(ry, pw) % period) % period;
+}
+__host__ __device__ inline int xinv_pipe_front(int ry, int pw, int lag, int period)
+{
+    const int pad = xinv_pipe_pad(ry, pw, period), room = lag * pw;
+    return (pad < room ? pad : room) & ~1;
+}
+__host__ __device__ inline int xinv_pipe_end(int ry, int pw, int lag, int period)
+{
+    return xinv_pipe_pad(ry, pw, period) - xinv_pipe_front(ry, pw, lag, period);
+}
+// first row the wavefront marches (relative to yu0) and the global step in which it enters
+__host__ __device__ inline int xinv_pipe_first_row(int ry, int pw, int lag, int period)
+{
+    return -8 + 2 * pw - xinv_pipe_front(ry, pw, lag, period);
+}
+__host__ __device__ inline int xinv_pipe_start(int ry, int pw, int lag, int period)
+{
+    return lag * pw - xinv_pipe_front(ry, pw, lag, period);
+}
+// Global step of the wavefront's first ring read (pw > 0).  Every row is taken out of the ring one step before it enters,
+// the first marched row therefore in step start - 1, before the barrier that may close that step; -1: the wavefront starts
+// in step 0 and its first read is row first + 1 in step 0 (the first marched row is then padding and stays zero).
+__host__ __device__ inline int xinv_pipe_first_read(int ry, int pw, int lag, int period)
+{
+    return xinv_pipe_start(ry, pw, lag, period) - 1;
+}
+__host__ __device__ inline int xinv_pipe_slot_flip(int front) { return front & 2; }
+// global steps every wavefront of the tile goes through: the longest of the four schedules, whole barrier periods
+// (period0: wavefront 0's unroll period, period: the others')
+__host__ __device__ inline int xinv_pipe_gtot(int ry, int lag, int b, int period0, int period)
+{
+    int gtot = 0;
+    for (int pw = 0; pw < 4; pw++) {
+        const int per = pw == 0 ? period0 : period;
+        const int g = xinv_pipe_start(ry, pw, lag, per) + xinv_pipe_rows(ry, pw) + xinv_pipe_pad(ry, pw, per);
+        gtot = g > gtot ? g : gtot;
+    }
+    return ((gtot + b - 1) / b) * b;
+}
+
 // ---- the planner's cost models (host only; pure integer / double arithmetic, checked on the CPU) --------------------------
 __host__ inline int64_t xinv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The tallest tile of the even split of yc rows into nrb blocks (xinv_tile_rows with RY == 0: boundaries at
+// floor(k yc / nrb) rounded down to even rows, the last block ends at yc), in closed form: with yc = 2 nrb q + s the
+// boundaries are 2 (k q + floor(k s / (2 nrb))); a block before the last has 2 q rows, or 2 q + 2 when the fraction
+// carries somewhere below the last boundary; the last block takes what is left.
+__host__ inline int64_t xinv_even_split_tallest(int64_t yc, int64_t nrb)
+{
+    const int64_t D = 2 * nrb, q = yc / D, s = yc - q * D;
+    const int64_t last = 2 * (q + s / 2 - ((nrb - 1) * s) / D) + (s & 1);
+    const int64_t inner = nrb > 1 ? 2 * (q + ((nrb - 1) * s >= D ? 1 : 0)) : 0;
+    return last > inner ? last : inner;
+}
 
 // Cost of a fused 2-D launch of `wgs` workgroups whose tiles own `rows` rows, in (workgroups per CU) x (steps per tile)
 // units: the model behind xinv_choose_row_blocks, shared with the masked-tile planner.  `occ` workgroups of the variant
@@ -175,14 +250,25 @@ __host__ inline int64_t xinv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b
 // `pipe_lag` > 0: the wave-pipelined pass (k_pipe2d: one tile per workgroup; pipe_lag = steps wavefront p+1 runs behind
 // wavefront p -- the last wavefront starts 3 x pipe_lag steps late and enters rows + 4 rows); 0: k_fused2d / k_fused9 at K
 // sweeps per pass.
-__host__ inline double xinv_tile_cost(int64_t wgs, int64_t rows, int K, int occ, int occ_cap, double lone, int pipe_lag)
+// `pipe_b` > 0 (with pipe_lag > 0; the kernel's steps per barrier): `rows` is the height of the TALLEST tile of the split
+// -- the launch ends with it -- and the steps are exactly the ones the kernel runs for it, xinv_pipe_gtot with the
+// kernel's unroll periods (pipe_per0: wavefront 0's, pipe_per: the others'; rows in flight + 4).
+// pipe_b == 0 keeps the estimate this model had before the schedule was shared -- `rows` the average height, one row added
+// for the even rounding, rounded up to 8 in one go -- for the plans recorded from it (tests/csrc/tiles_check.cpp).
+__host__ inline int64_t xinv_tile_steps(int64_t rows, int K, int pipe_lag, int pipe_b = 0, int pipe_per0 = 8, int pipe_per = 8)
+{
+    if (pipe_lag > 0 && pipe_b > 0) return xinv_pipe_gtot((int)rows, pipe_lag, pipe_b, pipe_per0, pipe_per);
+    const int64_t period = 2 * K + 2;
+    return pipe_lag > 0 ? xinv_cdiv(rows + 1 + 4 + 3 * pipe_lag, 8) * 8 : xinv_cdiv(rows + 1 + 4 * K, period) * period;
+}
+__host__ inline double xinv_tile_cost(int64_t wgs, int64_t rows, int K, int occ, int occ_cap, double lone, int pipe_lag,
+                                      int pipe_b = 0, int pipe_per0 = 8, int pipe_per = 8)
 {
     const bool pipe = pipe_lag > 0;
     occ = occ < occ_cap ? occ : occ_cap;
     occ = occ > 1 ? occ : 1;
-    const int64_t cap = 256 * (int64_t)occ, period = pipe ? 4 : 2 * K + 2;
-    const int64_t steps = pipe ? xinv_cdiv(rows + 1 + 4 + 3 * pipe_lag, 8) * 8               // +1: even rounding
-                               : xinv_cdiv(rows + 1 + 4 * K, period) * period;
+    const int64_t cap = 256 * (int64_t)occ;
+    const int64_t steps = xinv_tile_steps(rows, K, pipe_lag, pipe_b, pipe_per0, pipe_per);
     // rounds of `cap` resident workgroups; inside a round a CU holds ceil(w/256) of them,
     // and a lone workgroup on a CU leaves issue slots idle (charged like `lone`: 1.6 for the
     // issue-bound variants with one or two vector streams, ~1 for the bandwidth-bound ones)
@@ -199,16 +285,17 @@ __host__ inline double xinv_tile_cost(int64_t wgs, int64_t rows, int K, int occ,
 // Number of row blocks for the fused 2-D kernels.  Tall tiles amortise the 4K recomputed halo
 // rows, but every CU should hold the same number of workgroups: `occ` of the chosen variant fit
 // per CU.  Minimise (workgroups per CU, in rounds of 256*occ resident ones) x (steps per tile): xinv_tile_cost;
-// rows are then split evenly over the blocks.
+// rows are then split evenly over the blocks (pipe_b > 0: the pipelined pass is costed by its tallest tile's exact steps).
 __host__ inline int64_t xinv_choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int K, int occ, int occ_cap,
-                                               double lone, int pipe_lag)
+                                               double lone, int pipe_lag, int pipe_b = 0, int pipe_per0 = 8, int pipe_per = 8)
 {
     const bool pipe = pipe_lag > 0;
     int64_t best = 1; double best_cost = 1e300;
     const int64_t n0 = xinv_cdiv(yc, pipe ? 512 : 128), nmin = n0 > 1 ? n0 : 1, nmax = nmin > yc / 4 ? nmin : yc / 4;
     for (int64_t nr = nmin; nr <= nmax; nr++) {
         const int64_t wgs = xinv_cdiv(nstrip * nr, pipe ? 1 : 4) * nbatch;
-        const double cost = xinv_tile_cost(wgs, xinv_cdiv(yc, nr), K, occ, occ_cap, lone, pipe_lag);
+        const int64_t rows = (pipe && pipe_b > 0) ? xinv_even_split_tallest(yc, nr) : xinv_cdiv(yc, nr);
+        const double cost = xinv_tile_cost(wgs, rows, K, occ, occ_cap, lone, pipe_lag, pipe_b, pipe_per0, pipe_per);
         if (cost <= best_cost * 1.0001) { best_cost = cost < best_cost ? cost : best_cost; best = nr; }   // ties: more, shorter tiles
     }
     return best;
