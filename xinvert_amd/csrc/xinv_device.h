@@ -175,6 +175,16 @@ __device__ __forceinline__ double xinv_add_abs_where(double a, double b, unsigne
     return a;
 }
 
+// the contracted finish of XINV_FLAG_FMA under a complete mask: a = fma(t, rq, a) in the lanes of `mask` (k_pipe2d, whose
+// masks come out of the plan's table)
+__device__ __forceinline__ double xinv_fma_where(double a, double t, double rq, unsigned long long mask)
+{
+    unsigned long long sv;
+    asm("s_and_saveexec_b64 %1, %4\n\tv_fma_f64 %0, %2, %3, %0\n\ts_mov_b64 exec, %1"
+        : "+v"(a), "=&s"(sv) : "v"(t), "s"(rq), "s"(mask) : "scc");
+    return a;
+}
+
 // The same with the compare folded in: a + b in the lanes of `rowmask` whose f differs from u (the reference's
 // `F[j,i] != undef` of the update predicate), a in the others -- v_cmpx writes the compare's result into EXEC, so
 // the predicate costs no scalar logic at all: s_and_saveexec, v_cmpx, v_add, s_mov.
@@ -203,6 +213,21 @@ __device__ __forceinline__ void xinv_norm_row(double &sx, double &sy, int &nx, i
         "v_cmpx_neq_f64_e32 vcc, %7, %5\n\tv_add_f64 %0, %0, |%5|\n\tv_add_u32 %2, %2, 1\n\ts_mov_b64 exec, %4\n\t"
         "v_cmpx_neq_f64_e32 vcc, %7, %6\n\tv_add_f64 %1, %1, |%6|\n\tv_add_u32 %3, %3, 1\n\ts_mov_b64 exec, %4"
         : "+v"(sx), "+v"(sy), "+v"(nx), "+v"(ny), "=&s"(sv) : "v"(x), "v"(y), "s"(u) : "vcc");
+}
+// The same with the sample count on the scalar unit (k_pipe2d): ownx / owny are the lanes that own their column, the only
+// ones whose share is kept, so the row's compare runs under them and the samples are the bits it leaves in EXEC -- one
+// wave-uniform count in an SGPR instead of an integer add per lane and column.  The magnitudes keep their per-lane
+// accumulators and their order (a lane that owns nothing stays +0.0).  Eleven instructions, four of them on the VALU.
+__device__ __forceinline__ void xinv_norm_row_own(double &sx, double &sy, int &n, double x, double y, double u,
+                                                  unsigned long long ownx, unsigned long long owny)
+{
+    unsigned long long sv;
+    asm("s_and_saveexec_b64 %3, %7\n\t"
+        "v_cmpx_neq_f64_e32 vcc, %6, %4\n\tv_add_f64 %0, %0, |%4|\n\ts_bcnt1_i32_b64 vcc_lo, exec\n\ts_add_u32 %2, %2, vcc_lo\n\t"
+        "s_and_b64 exec, %3, %8\n\t"
+        "v_cmpx_neq_f64_e32 vcc, %6, %5\n\tv_add_f64 %1, %1, |%5|\n\ts_bcnt1_i32_b64 vcc_lo, exec\n\ts_add_u32 %2, %2, vcc_lo\n\t"
+        "s_mov_b64 exec, %3"
+        : "+v"(sx), "+v"(sy), "+s"(n), "=&s"(sv) : "v"(x), "v"(y), "s"(u), "s"(ownx), "s"(owny) : "vcc", "scc");
 }
 
 // Scalars of one solve (same for every member), passed by value to the kernels.

@@ -106,6 +106,8 @@ struct FusedArgs {
     const double *xsum;        // [nbatch] sum |S| over the skipped tiles (S != undef)
     const long long *xcnt;     // [nbatch] their sample count
     const void *rowf;          // k_pipe2d: [nbatch][yc] per-row records (M::PIPE_RW doubles each, xinv_pipe2d.h)
+    const unsigned long long *pmask;   // k_pipe2d: [nbatch][nstrip][yc] update masks, two lane words each (xinv_tiles.h:
+                               // xinv_pipe_mask_index; k_pipe_masks builds them once per plan)
     double *dbg;               // test-hooks build only: the hook record {tile, launch tag, member} (xinv_hook_withhold);
                                // test-hooks build (XINV_TEST_HOOKS): three ints {tile, launch tag, member} -- that tile of
                                // that launch withholds its norm partial, so that the reducer REALLY times out
@@ -328,6 +330,10 @@ struct FusedGen2D {                 // numbas.invert_general_2D, B == 0
     // wave-pipelined pass: the update of a row reads only its own per-row record, so it is asked for one step
     // ahead (fewer records live in SGPRs)
     static constexpr int PIPE_PFR = 1;
+    // ... and the norm's sample count stays on the VALU there: the march of this form holds six words of record per row
+    // in SGPRs, the count's two ownership masks and its counter no longer fit (v_readlane 229 -> 331 in the kernel) and
+    // the 8-member C4 row lost 10 % with it (profiles/pipe2d_solve_constants.txt)
+    static constexpr bool PIPE_SCOUNT = false;
 
     // every operand of the predicate (numbas.py:1126-1129) sits on the point itself: row r-1 is
     // handled here like in the other models (its first half-sweep runs in this very step)
@@ -524,6 +530,10 @@ using FusedGen2DQ = FusedGen2DQ_<false>;
 using FusedGen2DQA = FusedGen2DQ_<true>;
 template <class M, class = void> struct ModelPQ { static constexpr bool value = false; };
 template <class M> struct ModelPQ<M, std::void_t<decltype(M::PQ)>> { static constexpr bool value = M::PQ; };
+
+// k_pipe2d: the norm's sample count on the scalar unit (default) or per lane on the VALU (M::PIPE_SCOUNT = false)
+template <class M, class = void> struct ModelScount { static constexpr bool value = true; };
+template <class M> struct ModelScount<M, std::void_t<decltype(M::PIPE_SCOUNT)>> { static constexpr bool value = M::PIPE_SCOUNT; };
 
 template <class M, class = void> struct ModelFma { static constexpr bool value = false; };
 template <class M> struct ModelFma<M, std::void_t<decltype(M::FMA)>> { static constexpr bool value = M::FMA; };

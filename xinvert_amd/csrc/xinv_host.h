@@ -330,6 +330,7 @@ struct Workspace {
     std::vector<int> h_pre;                                     // plan_tile_skip: prefix counts (kept: no allocation per solve)
     double *d_tsum = nullptr; size_t d_tsum_cap = 0;            // tsum | tcnt | xsum | xcnt
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;              // k_pipe2d: per-row records [nbatch][yc][PIPE_RW]
+    unsigned long long *d_pmask = nullptr; size_t d_pmask_cap = 0;   // k_pipe2d: update masks [nbatch][nstrip][yc][2] (k_pipe_masks)
     double *d_pfac = nullptr; size_t d_pfac_cap = 0;            // k_pipe2d<FusedGen2DQ>: the point-factor stream Q [nbatch][yc][xc]
     void *wd_part = nullptr; size_t wd_part_cap = 0;            // watchdog recovery: partials of the separate norm kernels
     double *tri = nullptr; size_t tri_cap = 0;                  // k_tridiag: buf1 (cyclic: and the two auxiliary solves) [nbatch][n]
@@ -404,6 +405,8 @@ struct Problem {
     int ncoef;
     unsigned rowconst;           // host entries: arrays given as one value per row (see xinv.h)
     unsigned f32;                // host entries: bit 0 = S, bit q+1 = coefficient q is FLOAT32 on the host (xinv_options.f32_mask)
+    bool masks_by_chunk;         // rolling host batch: the members' forcing arrives chunk by chunk, after the plan -- make_plan
+                                 // leaves the pipelined pass's update masks (k_pipe_masks) to roll_join, chunk by chunk
     unsigned known_um;           // bit q: coefficient q is known to be constant along x (a resident plan expanded it from one
                                  // value per row itself: xinv_plan_create_*, rowconst_mask) -- the detection pass does not read it
     int BCz, BCy, BCx;

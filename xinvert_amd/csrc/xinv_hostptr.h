@@ -566,7 +566,9 @@ static int roll_plan(HostCall &h, Roll &R, bool *declined)
         // 2-D: the plan of a batch reads every member's forcing (the lists of fully masked tiles) -- the rolling batch plans
         // before they have arrived.  The first chunk is planned alone: if IT has masked tiles to skip, the chunk scheme
         // takes the call; else the batch is planned without tile lists (a later member's masked tiles are swept like any
-        // other: the update leaves masked points alone, the result is the same).
+        // other: the update leaves masked points alone, the result is the same).  The pipelined pass's table of update
+        // masks reads every member's forcing as well: the plan only allocates it, and every chunk's share is built when the
+        // chunk joins its lane, behind its upload (roll_join).
         Problem d1 = h.d; d1.nbatch = h.chunks[0];
         Plan pa;
         if ((r = make_plan(d1, h.o1, h.ws, h.scp, pa))) return r;
@@ -577,7 +579,11 @@ static int roll_plan(HostCall &h, Roll &R, bool *declined)
             if (h.d.c[q] && h.d.sc[q] == 0 && ((t_detected_um >> q) & 1u)) h.d.known_um |= 1u << q;
         oroll.flags |= XINV_FLAG_NO_TILE_SKIP;
     }
-    if ((r = make_plan(h.d, oroll, h.ws, h.scp, R.pl))) return r;
+    {
+        Problem dr = h.d;                            // (the flag only for THIS plan: the chunk scheme, if it takes the call after
+        dr.masks_by_chunk = h.roll2d;                //  all, plans each chunk whole)
+        if ((r = make_plan(dr, oroll, h.ws, h.scp, R.pl))) return r;
+    }
     if (R.pl.path != XINV_PATH_FUSED || R.pl.skip || R.pl.pq) {
         if (h.roll2d) { *declined = true; return XINV_OK; }
         t_err = "internal: rolling batch without a streaming kernel";
@@ -632,6 +638,9 @@ static int roll_join(HostCall &h, Roll &R, int64_t i)
     for (int l = 0; l < R.nl; l++)
         for (Lane &ln = R.lanes[l]; ln.cj < cn[l]; ln.cj++) {
             HIPCHK(hipStreamWaitEvent(ln.s, h.e_chunk[(size_t)ln.cj], 0));
+            if (h.roll2d)                            // (its forcing has arrived: the chunk's share of the update masks)
+                if (int r = launch_pipe_masks(h.d, R.pl, h.ws, ln.s, h.first[(size_t)ln.cj],
+                                              h.first[(size_t)ln.cj + 1] - h.first[(size_t)ln.cj])) return r;
             for (int64_t m = h.first[(size_t)ln.cj]; m < h.first[(size_t)ln.cj + 1]; m++) R.join[(size_t)m] = i;
             ln.hi = h.first[(size_t)ln.cj + 1];
         }

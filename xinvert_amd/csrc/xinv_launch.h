@@ -44,6 +44,8 @@ struct Plan {
     bool pq;                 // general form with A, C varying along x: the point-factor stream Q (FusedGen2DQ: relaxation
                              // factor and update predicate of every point, evaluated once per coefficient stack);
                              // Q lives in ws->d_pfac (a plan's own buffer while it solves)
+    bool pmask;              // `pipe`, hoisted march: the table of update masks in ws->d_pmask (k_pipe_masks) ...
+    int pm_rw, pm_irok;      // ... built from k_row_factor's records: doubles per record, the row predicate's word
 };
 
 // kernel variants instantiated per model: mask of streams read as one scalar per row
@@ -223,7 +225,7 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
         a.c[sm.forcing + 1] = a.c[sm.forcing]; a.sc[sm.forcing + 1] = a.sc[sm.forcing];
         a.c[sm.forcing] = (const double *)ws->d_pfac; a.sc[sm.forcing] = p.yc * p.xc;
     }
-    if (pipe) { a.nwg = a.nstrip * a.nrb; a.rowf = ws->d_rowf; }
+    if (pipe) { a.nwg = a.nstrip * a.nrb; a.rowf = ws->d_rowf; a.pmask = ws->d_pmask; }
 #if XINV_TEST_HOOKS
     a.dbg = (double *)t_hook_record;                 // (run_sweeps: XINV_HOOK_SKIP_PUBLISH; nullptr otherwise)
 #endif
@@ -241,6 +243,31 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
         }
         if (fused_dispatch(p.kind, pl.aligned, a.ext != 0, pl.um | (pl.alias_ac ? 2u : 0u), K, grid, block, st, a, nullptr, pl.seam != 0, pl.fma, pl.pq))
             return fail_arg("unsupported sweeps_per_launch for this kernel variant");
+        return XINV_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return XINV_OK;
+}
+
+// The update masks of the pipelined pass for members [member0, member0 + nmem): k_row_factor's records are complete on `st`
+// and those members' forcing is in place.  make_plan builds the whole batch's; the rolling host batch, whose members'
+// forcing arrives chunk by chunk, builds each chunk's when it joins (Problem::masks_by_chunk, roll_join).
+static int launch_pipe_masks(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem)
+{
+    if (!pl.pmask) return XINV_OK;
+    const StreamMap &sm = stream_map(p.kind);
+    PipeMaskArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.f = p.c[sm.c[sm.forcing]]; ma.sf = p.sc[sm.c[sm.forcing]];
+    ma.rowf = (const double *)ws->d_rowf; ma.rw = pl.pm_rw; ma.irok = pl.pm_irok;
+    ma.yc = p.yc; ma.xc = p.xc;
+    ma.per = (p.BCx == XINV_BC_PERIODIC); ma.al = pl.aligned; ma.seam = pl.seam != 0;
+    ma.nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    ma.undef = p.sc_.undef; ma.mask = ws->d_pmask;
+    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        ma.member0 = m;
+        hipLaunchKernelGGL(k_pipe_masks, dim3((unsigned)cdiv(p.yc, 4), (unsigned)ma.nstrip, (unsigned)nm), dim3(256), 0, st, ma);
         return XINV_OK;
     });
     if (rc) return rc;

@@ -64,12 +64,20 @@
 #ifndef XINV_PIPE_PF
 #define XINV_PIPE_PF 4            /* rows of F in flight, wavefronts 1..3 */
 #endif
+#ifndef XINV_PIPE_ST_AUX
+/* cache policy of wavefront 3's 16-byte stores of S (aligned strips): 16 = sc1, write-through -- the 40 MB of S a launch
+   stores are then not left dirty in the L2s for the kernel boundary to write back; 0 = write-back: 0.9 us per launch
+   slower at 3600x1800.  The 8-byte stores of the unaligned strips (odd xc: the seam tiles) stay write-back: written
+   through they cost the 3601-column row 14 % (profiles/pipe2d_solve_constants.txt) */
+#define XINV_PIPE_ST_AUX 16
+#endif
 
 // What a row needs besides S and the vector streams: one record per row, read through the scalar unit --
 // the values of the coefficient streams that are constant along x (bit q of UM), in stream order, then, when the
 // model's denominator is x-uniform (M::hoist<UM>()), the row's relaxation factor and the row part of the update
-// predicate (all ones / zero: all 64 bits are read, so no half of a load in flight is ever reused).  Padded to 4 or 8
-// doubles.  Standard form, A and C per row: {A[j], C[j], rq, rok}; general form, A C D E F per row:
+// predicate (all ones / zero).  The predicate word is there for k_pipe_masks, which folds it into the table of update
+// masks; the march takes the masks and does not use the word (dropping it would shrink no record: 3 -> 4, 6 -> 8 doubles).
+// Padded to 4 or 8 doubles.  Standard form, A and C per row: {A[j], C[j], rq, rok}; general form, A C D E F per row:
 // {A, C, D, E, F, rq, rok, -}; general form, D E F per row (A, C, G streamed): {D, E, F, -}; no record when
 // nothing is uniform.
 template <class M, unsigned UM> struct PipeRec {
@@ -129,6 +137,46 @@ __global__ __launch_bounds__(256) void k_row_factor(RowFactorArgs a)
         f[k++] = rq; f[k++] = rok;
     }
     for (; k < a.rw; k++) f[k] = 0.0;
+}
+#endif
+
+// The update predicate of the hoisted march is fixed for the life of a plan -- (column may be updated) & (row may be
+// updated: the record's predicate word) & (forcing defined: its mask may not change under a plan) -- so it is
+// evaluated ONCE, into a table of lane masks (xinv_tiles.h: xinv_pipe_mask_index), and the march reads two scalar words
+// per row instead of comparing the forcing with undef in every half-sweep.
+struct PipeMaskArgs {
+    const double *f;              // the forcing
+    int64_t sf;                   // its batch stride (0 = shared)
+    const double *rowf;           // k_row_factor's records [nbatch][yc][rw]; word `irok` is the row predicate
+    int rw, irok;
+    int64_t yc, xc;
+    int per, al, seam, nstrip;    // the launch's lane -> column map: periodic x, aligned strips, the seam's ring layout
+    double undef;
+    int64_t member0;              // first member of this launch
+    unsigned long long *mask;
+};
+#ifdef XINV_AUX_KERNELS
+// one wavefront per (row, strip, member); the lane's columns are those of the march (make_lanecols / make_lanecols_ring)
+__global__ __launch_bounds__(256) void k_pipe_masks(PipeMaskArgs a)
+{
+    constexpr int H = 2 * XINV_PIPE_P;
+    const int lane = threadIdx.x & 63, strip = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), m = a.member0 + blockIdx.z;
+    if (j >= a.yc) return;
+    const int UW = a.seam ? xinv_ring_uw(a.xc, H) : XINV_PIPE_UW(1), HW = a.seam ? xinv_ring_hw(a.xc, H, strip) : H;
+    const int64_t xu0 = (int64_t)strip * UW;
+    RingSeam rs = {0ull, false};
+    const LaneCols lc = a.seam ? make_lanecols_ring(xu0, HW, UW, lane, a.xc, rs)
+                        : (a.al ? make_lanecols<true>(xu0, H, UW, lane, a.xc, a.per != 0)
+                                : make_lanecols<false>(xu0, H, UW, lane, a.xc, a.per != 0));
+    const bool rok = __double_as_longlong(a.rowf[(m * a.yc + j) * a.rw + a.irok]) != 0;
+    const double *f = a.f + m * a.sf + j * a.xc;
+    const unsigned long long mx = __builtin_amdgcn_ballot_w64(rok && lc.ok_x && f[lc.l0] != a.undef);
+    const unsigned long long my = __builtin_amdgcn_ballot_w64(rok && lc.ok_y && f[lc.l1] != a.undef);
+    if (lane == 0) {
+        unsigned long long *q = a.mask + xinv_pipe_mask_index(m, a.nstrip, strip, a.yc, j);
+        q[0] = mx; q[1] = my;
+    }
 }
 #endif
 
@@ -227,7 +275,7 @@ __device__ __forceinline__ void pipe_extend_fix(double2 &edge, const double2 &in
 // pass for them alone (east operand: the next lane's .x, the new column 0), after which the phantom column mirrors
 // column xc-1 again.  Only the tiles that hold a seam lane are marched with SEAM = true (k_pipe2d below).
 template <class M, unsigned UM, bool FR, int NP, bool AL, bool EXT, int PW, int PF, bool SEAM = false>
-__device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, int yu0, int yu1,
+__device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, int strip, int yu0, int yu1,
                                                const LaneCols (&lc)[NP], const int64_t (&st0)[NP], int lane,
                                                double2 (*ring)[XINV_PIPE_NS][NP * (FR ? 2 : 1)][XINV_WAVE], int gtot,
                                                double &acc, int &cnt,
@@ -265,14 +313,17 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
         so1[q] = lc[q].use_y ? (unsigned)(st0[q] + 1) * 8u : 0xffffffffu;  //  resource's range -- the store is dropped)
     }
 
-    unsigned long long okx64[NP], oky64[NP];             // "column may be updated" as 64-bit lane masks (SGPR pairs)
+    unsigned long long ownx[NP], owny[NP];               // "lane owns its column" as 64-bit lane masks (SGPR pairs)
     double nsx[NP], nsy[NP];                             // norm share per lane and column
-    int nnx[NP], nny[NP];
+    int nn = 0;                                          // its samples: one count per wavefront, on the scalar unit ...
+    constexpr bool SCOUNT = ModelScount<M>::value;
+    int nnx[NP], nny[NP];                                // ... or, for the models that say so, per lane and column
 #pragma unroll
     for (int q = 0; q < NP; q++) {
-        okx64[q] = __builtin_amdgcn_ballot_w64(lc[q].ok_x) & ~seam_lanes; oky64[q] = __builtin_amdgcn_ballot_w64(lc[q].ok_y);
+        ownx[q] = __builtin_amdgcn_ballot_w64(lc[q].use_x); owny[q] = __builtin_amdgcn_ballot_w64(lc[q].use_y);
         nsx[q] = nsy[q] = 0.0; nnx[q] = nny[q] = 0;
     }
+    static_assert(NP == 1 || !PipeRec<M, UM>::HOIST, "the table of update masks holds one column pair per lane");
     static_assert(!SEAM || (NP == 1 && !AL && PipeRec<M, UM>::HOIST),
                   "seam variants: one column pair per lane, per-row records, updates under EXEC masks");
 
@@ -294,10 +345,10 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
 
     double2 sw[NP][R];
     CoefWin<NC, R> cw[NP];
-    double rokw[R];
+    unsigned long long mkx[R], mky[R];                   // the rows' update masks (HOIST: out of the plan's table)
 #pragma unroll
     for (int t = 0; t < R; t++) {
-        rokw[t] = 0.0;
+        mkx[t] = mky[t] = 0ull;
 #pragma unroll
         for (int q = 0; q < NP; q++) {
             sw[q][t] = make_double2(0.0, 0.0);
@@ -314,6 +365,10 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     const int maxo = (int)(rowbytes * (unsigned)(ycr - 1));
     int nxo = in_lo * (int)rowbytes;
     int nxr = in_lo * (RW * 8);                          // the same for the per-row records
+    int nxm = in_lo * (XINV_PIPE_MASK_WORDS * 8);        // and for the rows' update masks
+    typedef unsigned long long xinv_v2ull __attribute__((ext_vector_type(2)));       // (one 16-byte scalar load)
+    typedef const xinv_v2ull __attribute__((address_space(4))) *xinv_cmask_ptr;
+    const xinv_cmask_ptr maskp = (xinv_cmask_ptr)(uintptr_t)(a.pmask + xinv_pipe_mask_index(m, a.nstrip, strip, a.yc, 0));
     // a row of one of the lane's column pairs
     auto ldrow = [&](__amdgpu_buffer_rsrc_t rs, int soff, auto qtag) {
         constexpr int q = decltype(qtag)::value;
@@ -358,8 +413,20 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
 #pragma unroll
                 for (int c = 0; c < NC - 1; c++)
                     if ((UM >> c) & 1u) cw[q].s[c][slot] = rec[k++];
-                if (HOIST) { cw[q].rq[slot] = rec[k]; rokw[slot] = rec[k + 1]; }
+                if (HOIST) cw[q].rq[slot] = rec[k];      // (rec[k + 1], the row predicate, is in the masks)
             }
+        }
+    };
+    // the masks of row r, asked for when the row enters -- one step before its first update: the barrier's lgkmcnt(0)
+    // waits for every scalar load within two steps anyway, and four SGPRs per row in flight are dear -- with one
+    // s_load_dwordx4, the row clamped like the record's (rows 0 and yc-1 hold zero words)
+    auto request_mask = [&](auto stag) {
+        constexpr int slot = decltype(stag)::value;
+        if constexpr (HOIST) {
+            const unsigned moff = (unsigned)min(max(nxm, 0), (ycr - 1) * (XINV_PIPE_MASK_WORDS * 8));
+            nxm += XINV_PIPE_MASK_WORDS * 8;
+            const xinv_v2ull w = *(xinv_cmask_ptr)((const char __attribute__((address_space(4))) *)maskp + moff);
+            mkx[slot] = w.x; mky[slot] = w.y;
         }
     };
     // (in row order, as in the loop: the vmcnt waits of the loop are computed against the worst path into it)
@@ -388,15 +455,14 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
             const double t = M::template inc<X, UM, R, false>(cw[q], sj, sjp, comp<X>(sw[q][sj]), comp<X>(sw[q][sjp]),
                                               comp<X>(sw[q][sjm]), w, e, a.sc_);
             if constexpr (HOIST) {
-                // the predicate: (column may be updated) & (row may be updated: the record's predicate word is all
-                // ones or zero, k_row_factor) as a 64-bit lane mask on the scalar unit, (forcing defined) by the
-                // compare that writes EXEC
-                const unsigned long long rm = (FIX ? seam_lanes : (X ? oky64[q] : okx64[q])) &
-                                              (unsigned long long)__double_as_longlong(rokw[sj]);
+                // the predicate -- (column may be updated) & (row may be updated) & (forcing defined) -- is the row's word
+                // of the plan's table (k_pipe_masks); the seam tiles split the .x word between their two passes
+                unsigned long long rm = X ? mky[sj] : mkx[sj];
+                if constexpr (SEAM && X == 0) rm = FIX ? (rm & seam_lanes) : (rm & ~seam_lanes);
                 if constexpr (ModelFma<M>::value)          // (t is the bracket before the relaxation factor: one fma finishes)
-                    nv[q] = xinv_fma_where_ne(comp<X>(sw[q][sj]), t, cw[q].rq[sj], comp<X>(cw[q].v[FQ][sj]), u, rm);
+                    nv[q] = xinv_fma_where(comp<X>(sw[q][sj]), t, cw[q].rq[sj], rm);
                 else
-                    nv[q] = xinv_add_where_ne(comp<X>(sw[q][sj]), t, comp<X>(cw[q].v[FQ][sj]), u, rm);
+                    nv[q] = xinv_add_where(comp<X>(sw[q][sj]), t, rm);
             } else {
                 const unsigned long long pm = __builtin_amdgcn_ballot_w64((X ? cw[q].my[sj] : cw[q].mx[sj]) != 0u);
                 nv[q] = xinv_add_where(comp<X>(sw[q][sj]), t, pm);
@@ -450,6 +516,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
             const int r = rb_ + U;
             request(r + PF, ITAG((U + PF) % R));
             request_rf(r + PFR, ITAG((U + PFR) % R));
+            request_mask(ITAG(U));
             if (PW > 0) {
 #pragma unroll
                 for (int q = 0; q < NP; q++) {
@@ -487,9 +554,10 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
 #pragma unroll
                     for (int q = 0; q < NP; q++) {
                         const double2 t = sw[q][sj];
-                        // magnitudes and samples per lane and column under `S != undef` as EXEC; the lanes that
-                        // do not own their column are discarded after the march
-                        xinv_norm_row(nsx[q], nsy[q], nnx[q], nny[q], t.x, t.y, u);
+                        // magnitudes per lane and column, samples per wavefront, under `S != undef` as EXEC in the lanes
+                        // that own their column
+                        if constexpr (SCOUNT) xinv_norm_row_own(nsx[q], nsy[q], nn, t.x, t.y, u, ownx[q], owny[q]);
+                        else xinv_norm_row(nsx[q], nsy[q], nnx[q], nny[q], t.x, t.y, u);   // (un-owned lanes: discarded below)
                     }
                 }
                 // ---- row r-2 leaves
@@ -509,7 +577,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
                         if (AL) {                            // (use_x == use_y on aligned strips; un-owned lanes are out of range)
                             const xinv_v4u tv = {(unsigned)__double2loint(t.x), (unsigned)__double2hiint(t.x),
                                                  (unsigned)__double2loint(t.y), (unsigned)__double2hiint(t.y)};
-                            __builtin_amdgcn_raw_buffer_store_b128(tv, rsD, (int)so0[q], doff, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(tv, rsD, (int)so0[q], doff, XINV_PIPE_ST_AUX);
                         } else {
                             const xinv_v2u tx = {(unsigned)__double2loint(t.x), (unsigned)__double2hiint(t.x)};
                             const xinv_v2u ty = {(unsigned)__double2loint(t.y), (unsigned)__double2hiint(t.y)};
@@ -529,11 +597,15 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     for (; g < gtot; g++) if ((g + 1) % B == 0) xinv_pipe_barrier();
 #undef RING
 #pragma unroll
-    for (int q = 0; q < NP; q++) {                       // only the columns this lane owns count
-        acc += (lc[q].use_x ? nsx[q] : 0.0);
-        acc += (lc[q].use_y ? nsy[q] : 0.0);
-        cnt += (lc[q].use_x ? nnx[q] : 0) + (lc[q].use_y ? nny[q] : 0);
+    for (int q = 0; q < NP; q++) {                       // (a lane that does not own a column has added nothing to it)
+        if constexpr (SCOUNT) { acc += nsx[q]; acc += nsy[q]; }
+        else {
+            acc += (lc[q].use_x ? nsx[q] : 0.0);
+            acc += (lc[q].use_y ? nsy[q] : 0.0);
+            nn += (lc[q].use_x ? nnx[q] : 0) + (lc[q].use_y ? nny[q] : 0);
+        }
     }
+    cnt += nn;                                           // SCOUNT: wave-uniform; else this lane's
 }
 
 template <class M, unsigned UM, bool FR, int NP, bool AL, bool EXT, bool SEAM = false>
@@ -608,10 +680,10 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
         const bool wraps = rs.any;
 #define XINV_PIPE_MARCH(SM) \
         switch (pwi) { \
-        case 0: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 0, XINV_PIPE_PF0, SM>(a, m, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        case 1: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 1, XINV_PIPE_PF, SM>(a, m, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        case 2: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 2, XINV_PIPE_PF, SM>(a, m, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        default: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 3, XINV_PIPE_PF, SM>(a, m, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 0: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 0, XINV_PIPE_PF0, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 1: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 1, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 2: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 2, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        default: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 3, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
         }
         if (wraps) { XINV_PIPE_MARCH(SEAM) } else { XINV_PIPE_MARCH(false) }
 #undef XINV_PIPE_MARCH
@@ -637,7 +709,8 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
     {
         unsigned long long *pw = a.psum + (size_t)m * XINV_KMAX * NB * XINV_PW;
         const double ws = xinv_wave_sum(acc);
-        const long long wc = xinv_wave_sum_ll((long long)cnt);
+        // (counted on the scalar unit: already the wavefront's)
+        const long long wc = ModelScount<M>::value ? (long long)cnt : xinv_wave_sum_ll((long long)cnt);
         if (lane == 0 && !xinv_hook_withhold(a.hook, T, tag, m)) {
             const unsigned long long hi = (unsigned long long)tag << 32;
             const unsigned long long bits = (unsigned long long)__double_as_longlong(ws);

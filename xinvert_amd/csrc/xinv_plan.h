@@ -384,7 +384,15 @@ static int plan5_row_records(const Problem &p, const xinv_options &, Workspace *
     ra.gen = gen ? 1 : 0; ra.um = pl.um; ra.hoist = hoist ? 1 : 0; ra.rw = rw;
     ra.yc = p.yc; ra.xc = p.xc; ra.sc_ = p.sc_; ra.rowf = (double *)ws->d_rowf;
     hipLaunchKernelGGL(k_row_factor, dim3(cdiv(p.yc, 256), (unsigned)p.nbatch, 1), dim3(256), 0, st, ra);
-    return XINV_OK;
+    if (!hoist) return XINV_OK;
+    // the hoisted march's update masks: the row predicate just written, the launch's lane -> column map, the forcing's mask
+    const int nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    const int rc2 = ensure_dev(&ws->d_pmask, &ws->d_pmask_cap,
+                               (size_t)xinv_pipe_mask_count(p.nbatch, nstrip, p.yc) * sizeof(unsigned long long));
+    if (rc2) return rc2;
+    pl.pmask = true; pl.pm_rw = rw; pl.pm_irok = nw - 1;
+    if (p.masks_by_chunk) return XINV_OK;                // (the forcing of the later chunks is not there yet: roll_join)
+    return launch_pipe_masks(p, pl, ws, st, 0, p.nbatch);
 }
 
 // Rows per tile (the cost model: xinv_tiles.h).

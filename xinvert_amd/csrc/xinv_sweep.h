@@ -733,6 +733,7 @@ static int solve_dev(Problem &p, double *flags, const xinv_options *opt_in, hipS
 // workspace for the duration of a solve (under the workspace lock).
 struct PlanBufs {
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;
+    unsigned long long *d_pmask = nullptr; size_t d_pmask_cap = 0;
     int *d_list = nullptr; size_t d_list_cap = 0;
     double *d_tsum = nullptr; size_t d_tsum_cap = 0;
     double *d_pfac = nullptr; size_t d_pfac_cap = 0;
@@ -742,6 +743,7 @@ struct BufSwap {                                         // the plan's buffers s
     static void sw(Workspace *w, PlanBufs *q)
     {
         std::swap(w->d_rowf, q->d_rowf); std::swap(w->d_rowf_cap, q->d_rowf_cap);
+        std::swap(w->d_pmask, q->d_pmask); std::swap(w->d_pmask_cap, q->d_pmask_cap);
         std::swap(w->d_list, q->d_list); std::swap(w->d_list_cap, q->d_list_cap);
         std::swap(w->d_tsum, q->d_tsum); std::swap(w->d_tsum_cap, q->d_tsum_cap);
         std::swap(w->d_pfac, q->d_pfac); std::swap(w->d_pfac_cap, q->d_pfac_cap);
@@ -795,6 +797,7 @@ static void plan_free(xinv_plan *h)
         (void)ws->tail.wait(nullptr, true);
     }
     if (h->bufs.d_rowf) (void)hipFree(h->bufs.d_rowf);
+    if (h->bufs.d_pmask) (void)hipFree(h->bufs.d_pmask);
     if (h->bufs.d_list) (void)hipFree(h->bufs.d_list);
     if (h->bufs.d_tsum) (void)hipFree(h->bufs.d_tsum);
     if (h->bufs.d_pfac) (void)hipFree(h->bufs.d_pfac);

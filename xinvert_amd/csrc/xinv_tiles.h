@@ -229,6 +229,19 @@ __host__ __device__ inline int xinv_pipe_gtot(int ry, int lag, int b, int period
     return ((gtot + b - 1) / b) * b;
 }
 
+// The update masks of the pipelined pass (k_pipe_masks builds the table once per plan, the march reads it through the
+// scalar unit): one record per member, strip and row, two 64-bit lane masks {mx, my} -- bit i: lane i's .x / .y point of
+// that row may be updated (column, row and `forcing defined`).  Index in 64-bit words; rows 0 and yc-1 hold zero words.
+#define XINV_PIPE_MASK_WORDS 2
+__host__ __device__ inline int64_t xinv_pipe_mask_count(int64_t nbatch, int nstrip, int64_t yc)
+{
+    return nbatch * nstrip * yc * XINV_PIPE_MASK_WORDS;
+}
+__host__ __device__ inline int64_t xinv_pipe_mask_index(int64_t m, int nstrip, int strip, int64_t yc, int64_t row)
+{
+    return ((m * nstrip + strip) * yc + row) * XINV_PIPE_MASK_WORDS;
+}
+
 // ---- the planner's cost models (host only; pure integer / double arithmetic, checked on the CPU) --------------------------
 __host__ inline int64_t xinv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
