@@ -52,6 +52,7 @@ extern "C" {
 #define XINV_PATH_WAVE1D 4   /* stats only: the 1-D form's register-resident kernel (k_std1d), whatever path was asked */
 #define XINV_PATH_DIRECT1D 5 /* the 1-D form only, on request: one tridiagonal solve per member (k_tridiag) instead of
                                 sweeps -- the fixed point the sweeps converge to; XINV_ERR_ARG for every other form */
+#define XINV_PATH_FOURIER2D 6 /* stats only: the direct Fourier solve of the 2-D standard form (xinv_fourier.h) */
 
 #define XINV_FLAG_NO_XUNIFORM 1  /* stream every coefficient array in full: do not look for rows
                                     that are constant along x                                    */
@@ -465,6 +466,35 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
  * Not covered: the biharmonic form and the 1-D form.  The prototypes live in a header of their own, which this one
  * includes: a caller of xinv.h has them. */
 #include "xinv_resid.h"
+
+/* ---- fourier: the 2-D standard form for periodic x, solved directly ------------------------------------------------
+ * The most common 2-D call -- the lat-lon Poisson problem: B == 0 (NULL), BCy fixed, BCx periodic, no mask, A and C
+ * functions of y alone -- needs no iteration.  A discrete Fourier transform along x decouples the 5-point operator into one
+ * real tridiagonal system in y per zonal wavenumber k (K = xc / 2 + 1 of them), with lambda_k = 4 sin^2(pi k / xc):
+ *   A[j] ratioSqr X[j-1] - ((A[j+1] + A[j]) ratioSqr + C[j] lambda_k) X[j] + A[j+1] ratioSqr X[j+1] = DFT(F[j,:] delxSqr)[k]
+ * on rows j = 1 .. yc-2, rows 0 and yc-1 of S being the (transformed) boundary values.  The result is the fixed point of
+ * the sweeps to rounding; rows 0 and yc-1 of S are not written.  No stop rule: flags[m] = {overflow, 0, 0}, overflow = 1
+ * when the member's solution holds a non-finite value (the Thomas recurrence runs without pivoting).
+ * Arguments: A and C travel as ONE VALUE PER ROW, [nbatch or 1][yc]; strides[4]: S, A, C, F in elements between two
+ * members, 0 = one copy shared by every member (not S); flags: host double[nbatch][3].  xc: a product of 2, 3 and 5, at
+ * most 4096 (the transform keeps a pair of rows in LDS); yc >= 3.  XINV_ERR_ARG otherwise -- xinv_last_error names the
+ * length and its offending factor --, for a null array or a short stride, and when any member holds `undef` at a point
+ * the solve reads (F and C on rows 1 .. yc-2, A on rows 1 .. yc-1, S on rows 0 and yc-1): that is checked on the device
+ * before anything is written, and then NO member's S is touched.
+ * _dev: device pointers, the current device, on `stream`; the call waits for the flags.  The spectrum and the forward
+ * factors live in one buffer per device, which the library owns and grows on demand; calls from several streams or
+ * threads take turns on it (the discipline of xinv_tridiag_f64_dev).  Not for stream capture.
+ * _batched: host pointers, the plain staging of the side families, on opt->device; f32_mask, prep_flags, rowconst_mask
+ * and ndev > 1 are refused.  xinv_stats.path = XINV_PATH_FOURIER2D.
+ *   xinv_fourier_standard_2d_f64_dev(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, flags, stream)
+ *   xinv_fourier_standard_2d_f64_batched(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, flags, opt)
+ * The row transform under it, for callers who want the spectrum: `nrows` packed real rows of n points <-> their half
+ * spectra, [nrows][n / 2 + 1] complex (re, im interleaved), numpy.fft.rfft / irfft along the last axis (the inverse
+ * ignores the imaginary parts of X[0] and X[n/2] and divides by n).  inverse = 0: in real, out spectrum; 1: the reverse.
+ * Not in place.  Device pointers; only queued on `stream`.
+ *   xinv_rowdft_f64_dev(out, in, nrows, n, inverse, stream)
+ * The prototypes live in a header of their own, which this one includes: a caller of xinv.h has them. */
+#include "xinv_fourier.h"
 
 /* ---- resident plans: what a solve derives from the coefficient stack, built once -------------------------------
  * The reference calls its kernel again and again on ONE coefficient stack: apps.animate_iteration (apps.py:1031-1044:

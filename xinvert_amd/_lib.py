@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get('XINV_SO') or os.path.join(HERE, 'libxinv_hip.so')
 
 BC_CODES = {'fixed': 0, 'extend': 1, 'periodic': 2}
-PATH_AUTO, PATH_COLOUR, PATH_FUSED, PATH_WAVE1D, PATH_DIRECT1D = 0, 1, 2, 4, 5
+PATH_AUTO, PATH_COLOUR, PATH_FUSED, PATH_WAVE1D, PATH_DIRECT1D, PATH_FOURIER2D = 0, 1, 2, 4, 5, 6
 PREP_MASK_NAN, PREP_MASK_VALUE, PREP_ROWSCALE, PREP_S_ZERO, PREP_DEMASK = 1, 2, 4, 8, 16     # XINV_PREP_*
 MAX_DEVICES = 16                      # XINV_MAX_DEVICES
 
@@ -80,6 +80,7 @@ EXPORTS = [
     'xinv_residual_standard_2d_test_f64_dev', 'xinv_residual_standard_2d_test_f64_batched',
     'xinv_residual_standard_3d_f64_dev', 'xinv_residual_standard_3d_f64_batched',
     'xinv_residual_general_3d_f64_dev', 'xinv_residual_general_3d_f64_batched',
+    'xinv_fourier_standard_2d_f64_dev', 'xinv_fourier_standard_2d_f64_batched', 'xinv_rowdft_f64_dev',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -131,6 +132,12 @@ def load():
     # prolong(coarse, fine, force, nbatch, ndim, cshape, fshape, idx, w, keep_edges, undef, stream)
     L.xinv_mg_restrict_f64_dev.argtypes = [_vp, _vp, _i64, _int, _ip, _ip, _f64, _vp]
     L.xinv_mg_prolong_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _int, _ip, _ip, _vp, _vp, _int, _f64, _vp]
+    # the Fourier solve: S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, flags (host), stream / opt;
+    # the row transform: out, in, nrows, n, inverse, stream
+    four_tail = [_i64, _ip, _i64, _i64, _f64, _f64, _f64, _dp]
+    L.xinv_fourier_standard_2d_f64_dev.argtypes = [_vp] * 4 + four_tail + [_vp]
+    L.xinv_fourier_standard_2d_f64_batched.argtypes = [_dp] * 4 + four_tail + [_opt]
+    L.xinv_rowdft_f64_dev.argtypes = [_vp, _vp, _i64, _i64, _int, _vp]
     L.xinv_plan_solve_f64_dev.argtypes = [_vp, _vp, _dp, _i64, _f64, _vp]
     L.xinv_plan_solve_frames_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _dp, _i64, _f64, _vp]
     L.xinv_plan_refresh.argtypes = [_vp, _vp]

@@ -60,6 +60,8 @@ UNITS = [
     ('xinv_tu_mg', 'xinv_tu_mg.hip', []),
     # the residual L(S) - F of the second-order forms: one streaming launch per call (k_resid2d, k_resid3d)
     ('xinv_tu_resid', 'xinv_tu_resid.hip', []),
+    # the direct Fourier solve of the 2-D standard form for periodic x (k_rowdft, k_fourier_tri, k_fourier_check)
+    ('xinv_tu_fourier', 'xinv_tu_fourier.hip', []),
 ]
 # XINV_VARIANT_UNITS="xinv_tu_fused3d,..." (with XINV_BUILD_TAG): only these units are compiled with the extra flags; every
 # other object is taken from the shipped build's build/obj (a variant of one kernel family links in seconds)
@@ -86,8 +88,8 @@ def hipcc():
 
 def _abi_headers():
     """include/xinv.h and the headers it includes (xinv_trace.h: the tridiagonal solver's prototypes; xinv_resid.h: the
-    residual's)."""
-    return [os.path.join(HERE, '..', 'include', f) for f in ('xinv.h', 'xinv_trace.h', 'xinv_resid.h')]
+    residual's; xinv_fourier.h: the Fourier solve's)."""
+    return [os.path.join(HERE, '..', 'include', f) for f in ('xinv.h', 'xinv_trace.h', 'xinv_resid.h', 'xinv_fourier.h')]
 
 
 def _headers():

@@ -173,13 +173,17 @@ def _prep_coef(c, F, perm, core_shape, nbatch, allow_null=False):
 
 
 def _method(kind, iParams):
-    """iParams['method']: 'sor' (default) or 'direct', which only the 1-D standard form has."""
+    """iParams['method']: 'sor' (default); 'direct', which only the 1-D standard form has; 'fourier', which only the 2-D
+    standard form has (xinvert_amd/fourier.py: periodic x, coefficients constant along x, no mask)."""
     method = iParams.get('method', 'sor')
-    if method not in ('sor', 'direct'):
-        raise Exception("iParams['method'] must be 'sor' or 'direct', got %r" % (method,))
+    if method not in ('sor', 'direct', 'fourier'):
+        raise Exception("iParams['method'] must be 'sor' or 'direct' (or 'fourier', for inv_standard2D), got %r" % (method,))
     if method == 'direct' and kind != 'std1d':
         raise Exception("iParams['method'] = 'direct' is available for the 1-D standard form only (inv_standard1D, "
                         "invert_GeoAdjustment, invert_RefStateSWM), not for %s" % forms.FORMS[kind].inv)
+    if method == 'fourier' and kind != 'std2d':
+        raise Exception("iParams['method'] = 'fourier' is available for the 2-D standard form only (inv_standard2D and the "
+                        "apps on it), not for %s; 'sor' solves this case" % forms.FORMS[kind].inv)
     return method
 
 
@@ -415,8 +419,56 @@ def _residual(kind, coefs, F, S, dims, iParams):
     return F.like(np.ascontiguousarray(out), 'residual')
 
 
+def _solve_fourier(coefs, F, S, dims, iParams):
+    """iParams['method'] = 'fourier': one call of xinv_fourier_standard_2d_f64_batched on every slice (float64; the forcing
+    built on the host; A and C travel as one value per row).  optArg, mxLoop and tolerance play no part; flags =
+    [overflow, 0, 0].  A call outside the path's scope raises before anything runs (fourier.eligible)."""
+    from . import fourier
+    if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
+        raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
+    devs = iParams.get('devices')
+    if devs is not None and (isinstance(devs, str) or len(list(devs)) > 1):
+        raise NotImplementedError("iParams['method'] = 'fourier' runs on one device: name it with iParams['device']")
+    perm, bdims, bshape = _batch_layout(F, dims)
+    core_shape = tuple(F.shape[F.axis(d)] for d in dims)
+    nbatch = int(np.prod(bshape)) if bshape else 1
+    yc, xc = core_shape
+    n = yc * xc
+    if nbatch == 0:
+        return S if S is not None else F.like(np.zeros(F.shape))
+    if S is None:
+        S = F.like(np.zeros(F.shape))
+    tr = lambda v: np.ascontiguousarray(np.transpose(np.asarray(v, dtype=np.float64), perm)).reshape((nbatch,) + core_shape)
+    Fv, Sv = tr(F.values), tr(S.values)
+    A, B, C = [_prep_coef(c, F, perm, core_shape, nbatch, allow_null=(k == 1)) for k, c in enumerate(coefs)]
+    Ar, Cr = fourier.eligible((A[0], A[2]), (B[0], B[2]), (C[0], C[2]), Fv, Sv, iParams['BCs'], _undeftmp)
+    L = _lib.require_gpu()
+    strides = [n, yc if Ar.ndim == 2 else 0, yc if Cr.ndim == 2 else 0, n]
+    flags = np.zeros((nbatch, 3))
+    rc = L.xinv_fourier_standard_2d_f64_batched(_lib.hptr(Sv), _lib.hptr(Ar), _lib.hptr(Cr), _lib.hptr(Fv), nbatch,
+                                                _lib.strides_arg(strides), yc, xc, float(iParams['del1Sqr']),
+                                                float(iParams['ratioSqr']), _undeftmp, _lib.hptr(flags),
+                                                _lib.options(device=int(iParams.get('device', -1))))
+    _lib.check(rc)
+    out = np.transpose(Sv.reshape(tuple(bshape) + core_shape), np.argsort(perm))
+    if S.values.dtype == out.dtype and S.values.flags.writeable:
+        S.values[...] = out
+    else:
+        S.values = np.ascontiguousarray(out)
+    iParams['flags'] = flags if nbatch > 1 else flags[0]
+    iParams['stats'] = _lib.last_stats()
+    if iParams.get('printInfo', True):
+        coords = [np.asarray(F[d]) for d in bdims]
+        for m, idx in enumerate(itertools.product(*coords) if bdims else [()]):
+            print(_info(dict(zip(bdims, idx))) + ' fourier solve' + (' (overflows!)' if flags[m, 0] else ''))
+    return S
+
+
 def _solve(kind, coefs, F, S, dims, iParams):
-    direct = _method(kind, iParams) == 'direct'
+    method = _method(kind, iParams)
+    if method == 'fourier':
+        return _solve_fourier(coefs, F, S, dims, iParams)
+    direct = method == 'direct'
     if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
         raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
     perm, bdims, bshape = _batch_layout(F, dims)

@@ -74,6 +74,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_fd_host.h"      /* finite-difference operators (k_fd) */
 #include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
 #include "xinv_resid_host.h"   /* the residual L(S) - F of the second-order forms (k_resid2d, k_resid3d) */
+#include "xinv_fourier_host.h" /* the direct Fourier solve of the 2-D standard form for periodic x (k_rowdft, k_fourier_tri) */
 
 // ------------------------------------------------------------------ C-ABI
 extern "C" {
@@ -513,6 +514,39 @@ int xinv_tridiag_f64_dev(double *x, const double *a, const double *b, const doub
                          const double *cn, int64_t nbatch, const int64_t *strides, int64_t n, void *stream)
 {
     GUARD(tridiag_solve_dev(mk_tridiag(x, a, b, c, d, a0, cn, nbatch, strides, n), strides, (hipStream_t)stream))
+}
+
+// ---- the direct Fourier solve of the 2-D standard form for periodic x (include/xinv_fourier.h) ----------------------
+static FourierCall mk_fourier(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
+                              const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr, double undef)
+{
+    FourierCall c;
+    memset(&c, 0, sizeof c);
+    c.S = S; c.A = A; c.C = C; c.F = F; c.nbatch = nbatch; c.yc = yc; c.xc = xc;
+    if (strides)
+        for (int q = 0; q < 4; q++) c.s[q] = strides[q];
+    c.delxSqr = delxSqr; c.ratioSqr = ratioSqr; c.undef = undef;
+    return c;
+}
+
+int xinv_fourier_standard_2d_f64_dev(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
+                                     const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr,
+                                     double undef, double *flags, void *stream)
+{
+    GUARD(fourier_dev(mk_fourier(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags,
+                      (hipStream_t)stream))
+}
+
+int xinv_fourier_standard_2d_f64_batched(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
+                                         const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr,
+                                         double undef, double *flags, const xinv_options *opt)
+{
+    GUARD(fourier_host(mk_fourier(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags, opt))
+}
+
+int xinv_rowdft_f64_dev(double *out, const double *in, int64_t nrows, int64_t n, int inverse, void *stream)
+{
+    GUARD(rowdft_dev(out, in, nrows, n, inverse, (hipStream_t)stream))
 }
 
 // ---- the residual L(S) - F of the five second-order forms (k_resid2d / k_resid3d; include/xinv_resid.h) ------------

@@ -1,0 +1,39 @@
+// xinv_tu_fourier.hip -- instantiations of k_rowdft / k_fourier_tri / k_fourier_check (the direct Fourier solve: xinv_fourier.h).
+#define XINV_FOURIER_KERNELS
+#include "xinv_fourier.h"
+
+#define FOURIER_MEMBER_CHUNK 32768    /* members per launch (grid.y <= 65535) */
+
+// 0, or the HIP error of raising the kernel's dynamic-LDS limit (a pair of n complex doubles passes 64 KiB at n = 2048)
+int xinv_launch_rowdft(const RowDftArgs &a, bool inverse, hipStream_t st)
+{
+    const size_t lds = (size_t)a.n * 32;
+    const void *fn = inverse ? (const void *)k_rowdft<true> : (const void *)k_rowdft<false>;
+    if (lds > 65536) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    const dim3 grid((unsigned)((a.nrows / a.rpm) * ((a.rpm + 1) / 2))), block(XINV_DFT_WG);
+    if (inverse) hipLaunchKernelGGL(k_rowdft<true>, grid, block, lds, st, a);
+    else hipLaunchKernelGGL(k_rowdft<false>, grid, block, lds, st, a);
+    return 0;
+}
+
+void xinv_launch_fourier_tri(FourierTriArgs a, int64_t nbatch, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((a.K + XINV_FTRI_WG - 1) / XINV_FTRI_WG);
+    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
+        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
+        a.member0 = m0;
+        hipLaunchKernelGGL(k_fourier_tri, dim3(gx, (unsigned)nm), dim3(XINV_FTRI_WG), 0, st, a);
+    }
+}
+
+void xinv_launch_fourier_check(FourierCheckArgs a, int64_t nbatch, hipStream_t st)
+{
+    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
+        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
+        a.member0 = m0;
+        hipLaunchKernelGGL(k_fourier_check, dim3((unsigned)a.yc, (unsigned)nm), dim3(XINV_FCHK_WG), 0, st, a);
+    }
+}
