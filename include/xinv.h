@@ -164,8 +164,7 @@ typedef struct xinv_stats {
     int32_t host_chunks;        /* member chunks the call was pipelined over (all devices)      */
     int32_t devices;            /* GPUs the batch was split over                                */
     int32_t pipelined;          /* fused 2-D path: the full passes ran the wave-pipelined kernel (k_pipe2d:
-                                   one tile per workgroup, one sweep per wavefront); value = column pairs
-                                   per lane (1 or 2), 0 = k_fused2d                              */
+                                   one tile per workgroup, one sweep per wavefront): 1, 0 = k_fused2d        */
     int32_t masked_tile_ppm;    /* masked_tile_pct at full resolution: skipped wave-tiles per million (bench.py prices
                                    its roofline on the tiles that ran)                           */
     int32_t recovered_members;  /* members whose in-kernel norm reduction timed out (watchdog) and that were finished

@@ -80,7 +80,7 @@ cmd="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu --no-parity --no-co
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/p_w -o r -- $cmd > /dev/null 2>&1
   python $R/tools/prof_summary.py counters $(db /tmp/p_f) $out/${RN}_pmc_fetch_bench.txt > /dev/null
   python $R/tools/prof_summary.py counters $(db /tmp/p_w) $out/${RN}_pmc_write_bench.txt > /dev/null
-  python $R/tools/prof_summary.py traffic $(db /tmp/p_f) $(db /tmp/p_w) "k_pipe2d<FusedStd2D, 3u, false, 1" std2d_pipe_um3 $out/traffic.json 1 1
+  python $R/tools/prof_summary.py traffic $(db /tmp/p_f) $(db /tmp/p_w) "k_pipe2d<FusedStd2D, 3u, false," std2d_pipe_um3 $out/traffic.json 1 1
   python $R/tools/prof_summary.py traffic $(db /tmp/p_f) $(db /tmp/p_w) "k_fused2d<FusedStd2D, 1" std2d_spl1_um0_all $out/traffic.json 8 2 )
 python -c "
 import json; d=json.load(open('$out/traffic.json')); print({k: (v if not isinstance(v, dict) else '...') for k, v in d.items() if not k.endswith('_detail') and k != 'configs'}); print({k: round(v['bytes_per_point_sweep'], 2) for k, v in d['configs'].items()}); print(d.get('std2d_spl1_um0_all_detail'))"

@@ -37,27 +37,27 @@ XINV_HIDDEN int xinv_launch_fused2d_genq(bool al, bool ext, unsigned um, int K, 
                                          hipStream_t st, const FusedArgs &a, int *occ);
 XINV_HIDDEN int xinv_launch_pipe2d_fma(bool gen, unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                        const FusedArgs &a, int *occ, int lds_pad);
-// wave-pipelined four-sweep pass, one tile per 256-thread workgroup: standard form (um = 3: A and C per row, np = 1
-// or 2 column pairs per lane) and general form (um = 0x1f: A C D E F per row).  Returns 1 for a variant that is
-// not instantiated (coefficient arrays varying along x: measured slower than k_fused2d, see plan_fused5).
+// wave-pipelined four-sweep pass, one tile per 256-thread workgroup: standard form (um = 3: A and C per row) and
+// general form (um = 0x1f: A C D E F per row).  Returns 1 for a variant that is not instantiated (coefficient
+// arrays varying along x: measured slower than k_fused2d, see plan_fused5).
 // lds_pad: unused dynamic LDS per workgroup, which caps how many of them share a CU (see launch_fused)
-// fr: the forcing row rides the LDS ring with S (per-row-coefficient variants, one column pair per lane)
-XINV_HIDDEN int xinv_launch_pipe2d_std(unsigned um, int np, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
+// fr: the forcing row rides the LDS ring with S
+XINV_HIDDEN int xinv_launch_pipe2d_std(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                        const FusedArgs &a, int *occ, int lds_pad);
-XINV_HIDDEN int xinv_launch_pipe2d_gen(unsigned um, int np, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
+XINV_HIDDEN int xinv_launch_pipe2d_gen(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                        const FusedArgs &a, int *occ, int lds_pad);
-XINV_HIDDEN int xinv_launch_pipe2d_std_seam(unsigned um, int np, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
+XINV_HIDDEN int xinv_launch_pipe2d_std_seam(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                             const FusedArgs &a, int *occ, int lds_pad);
-XINV_HIDDEN int xinv_launch_pipe2d_gen_seam(unsigned um, int np, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
+XINV_HIDDEN int xinv_launch_pipe2d_gen_seam(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                             const FusedArgs &a, int *occ, int lds_pad);
-static inline int xinv_launch_pipe2d(bool gen, unsigned um, int np, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
+static inline int xinv_launch_pipe2d(bool gen, unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st,
                                      const FusedArgs &a, int *occ, int lds_pad = 0, bool seam = false, bool fma = false)
 {
-    if (fma) return (seam || np != 1) ? 1 : xinv_launch_pipe2d_fma(gen, um, fr, al, ext, grid, st, a, occ, lds_pad);
-    if (seam) return gen ? xinv_launch_pipe2d_gen_seam(um, np, fr, al, ext, grid, st, a, occ, lds_pad)
-                         : xinv_launch_pipe2d_std_seam(um, np, fr, al, ext, grid, st, a, occ, lds_pad);
-    return gen ? xinv_launch_pipe2d_gen(um, np, fr, al, ext, grid, st, a, occ, lds_pad)
-               : xinv_launch_pipe2d_std(um, np, fr, al, ext, grid, st, a, occ, lds_pad);
+    if (fma) return seam ? 1 : xinv_launch_pipe2d_fma(gen, um, fr, al, ext, grid, st, a, occ, lds_pad);
+    if (seam) return gen ? xinv_launch_pipe2d_gen_seam(um, fr, al, ext, grid, st, a, occ, lds_pad)
+                         : xinv_launch_pipe2d_std_seam(um, fr, al, ext, grid, st, a, occ, lds_pad);
+    return gen ? xinv_launch_pipe2d_gen(um, fr, al, ext, grid, st, a, occ, lds_pad)
+               : xinv_launch_pipe2d_std(um, fr, al, ext, grid, st, a, occ, lds_pad);
 }
 XINV_HIDDEN int xinv_launch_fused9(bool gen, int K, bool al, bool ext, dim3 grid, hipStream_t st,
                                    const FusedArgs &a, int *occ, bool seam = false);

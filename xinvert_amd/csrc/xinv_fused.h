@@ -484,7 +484,6 @@ template <bool AC> struct FusedGen2DQ_ {
     static constexpr bool PQ = true;
     static constexpr int QI = 5;                         // stream index of Q
     template <unsigned UM> static constexpr bool hoist() { return false; }
-    static constexpr int PIPE_PFR = 1;
     template <unsigned UM, int D, bool PRE = true>
     static __device__ __forceinline__ void derive(CoefWin<NC, D> &w, int, int s1, bool okx, bool oky, const XinvScal &)
     {
@@ -555,13 +554,12 @@ __device__ __forceinline__ double2 ld2(const double *p, int64_t row_off, const L
 }
 
 // Lane -> column map of one wavefront's strip: lane owns columns c0 = xu0 - H + 2*lane and c0+1.
-// (np column pairs per lane, this is pair q: k_pipe2d's wide strips; np = 1, q = 0 everywhere else)
 template <bool AL>
 __device__ __forceinline__ LaneCols make_lanecols(int64_t xu0, int H, int UW, int lane, int64_t xc,
-                                                  bool per, int np = 1, int q = 0)
+                                                  bool per)
 {
     LaneCols lc;
-    const int64_t c0 = xu0 - H + 2 * np * lane + 2 * q, c1 = c0 + 1;
+    const int64_t c0 = xu0 - H + 2 * lane, c1 = c0 + 1;
     if (per) {
         int64_t w0 = c0 % xc; if (w0 < 0) w0 += xc;
         int64_t w1 = c1 % xc; if (w1 < 0) w1 += xc;

@@ -331,7 +331,7 @@ struct Workspace {
     double *d_tsum = nullptr; size_t d_tsum_cap = 0;            // tsum | tcnt | xsum | xcnt
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;              // k_pipe2d: per-row records [nbatch][yc][PIPE_RW]
     unsigned long long *d_pmask = nullptr; size_t d_pmask_cap = 0;   // k_pipe2d: update masks [nbatch][nstrip][yc][2] (k_pipe_masks)
-    double *d_pfac = nullptr; size_t d_pfac_cap = 0;            // k_pipe2d<FusedGen2DQ>: the point-factor stream Q [nbatch][yc][xc]
+    double *d_pfac = nullptr; size_t d_pfac_cap = 0;            // k_fused2d<FusedGen2DQ>: the point-factor stream Q [nbatch][yc][xc]
     void *wd_part = nullptr; size_t wd_part_cap = 0;            // watchdog recovery: partials of the separate norm kernels
     double *tri = nullptr; size_t tri_cap = 0;                  // k_tridiag: buf1 (cyclic: and the two auxiliary solves) [nbatch][n]
     int *tri_ovf = nullptr; size_t tri_ovf_cap = 0;             // ... the direct 1-D solve's overflow words [nbatch]

@@ -36,7 +36,6 @@ struct Plan {
     double lone = 1.6;       // planner: cost of a workgroup alone on its CU relative to one of a pair
     bool pipe;               // K == 4 passes run the wave-pipelined kernel (k_pipe2d): one tile per workgroup
     int tpw;                 // wave-tiles per workgroup of the planned kernel: 4, or 1 with `pipe`
-    int npair;               // `pipe`: column pairs per lane (1 or 2: strips of 112 or 240 owned columns)
     bool pipe_fr;            // `pipe`: the forcing rides the LDS ring (launches whose arrays exceed the caches)
     int64_t xc;              // the problem's row length (the ring layout's strip width depends on it: xinv_tiles.h)
     bool fma;                // XINV_FLAG_FMA: the contracted-arithmetic kernel variants (per-row-coefficient forms only)
@@ -44,8 +43,6 @@ struct Plan {
     bool pq;                 // general form with A, C varying along x: the point-factor stream Q (FusedGen2DQ: relaxation
                              // factor and update predicate of every point, evaluated once per coefficient stack);
                              // Q lives in ws->d_pfac (a plan's own buffer while it solves)
-    bool pmask;              // `pipe`, hoisted march: the table of update masks in ws->d_pmask (k_pipe_masks) ...
-    int pm_rw, pm_irok;      // ... built from k_row_factor's records: doubles per record, the row predicate's word
 };
 
 // kernel variants instantiated per model: mask of streams read as one scalar per row
@@ -72,13 +69,22 @@ static const StreamMap &stream_map(int kind)
 }
 
 // edge strips whose row blocks are cut in two for a tiling of `nstrip` strips (one strip spans the row: it is both)
-// columns a tile owns: 128 minus the 2K halo columns a side; the wave-pipelined pass has K = 4 and np column pairs per
-// lane; the odd-xc periodic seam variants own one pair less (k_fused2d: SEAM)
+// columns a tile owns: 128 minus the 2K halo columns a side (the wave-pipelined pass has K = 4); the odd-xc periodic
+// seam variants own one pair less (k_fused2d: SEAM)
 static inline int strip_uw(const Plan &pl, int K, bool pipe)
 {
     // (odd-xc periodic seam: the ring layout's strips, xinv_tiles.h)
     if (pl.seam) return xinv_ring_uw(pl.xc, pipe ? 2 * XINV_PIPE_P : 2 * K);
-    return pipe ? XINV_PIPE_UW(pl.npair) : 128 - 4 * K;
+    return pipe ? XINV_PIPE_UW : 128 - 4 * K;
+}
+
+// k_row_factor's record of the two pipelined forms (xinv_pipe2d.h: PipeRec): doubles per record, the row predicate's word
+struct PipeRecShape { int rw, irok; };
+static inline PipeRecShape pipe_rec_shape(int kind)
+{
+    using G = PipeRec<FusedGen2D, 0x1fu>;
+    using S = PipeRec<FusedStd2D, 3u>;
+    return kind == KIND_GEN2D ? PipeRecShape{G::RW, G::NW - 1} : PipeRecShape{S::RW, S::NW - 1};
 }
 
 // k_pipe3d's launch shape (which tiles of a launch march the whole column, which are cut into the plan's k chunks) and the
@@ -238,7 +244,7 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
             // (XINV_PIPE_LDSPAD: unused dynamic LDS per workgroup, to cap the workgroups per CU in experiments;
             //  capping at the planned count changed nothing: the dispatcher already spreads them evenly)
             const int pad = std::max(0, XINV_ENV_INT("XINV_PIPE_LDSPAD", 0));
-            xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.npair, pl.pipe_fr, pl.aligned, a.ext != 0, grid, st, a, nullptr, pad, pl.seam != 0, pl.fma);
+            xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.pipe_fr, pl.aligned, a.ext != 0, grid, st, a, nullptr, pad, pl.seam != 0, pl.fma);
             return XINV_OK;
         }
         if (fused_dispatch(p.kind, pl.aligned, a.ext != 0, pl.um | (pl.alias_ac ? 2u : 0u), K, grid, block, st, a, nullptr, pl.seam != 0, pl.fma, pl.pq))
@@ -255,12 +261,12 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
 // forcing arrives chunk by chunk, builds each chunk's when it joins (Problem::masks_by_chunk, roll_join).
 static int launch_pipe_masks(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem)
 {
-    if (!pl.pmask) return XINV_OK;
+    if (!pl.pipe) return XINV_OK;
     const StreamMap &sm = stream_map(p.kind);
     PipeMaskArgs ma;
     memset(&ma, 0, sizeof ma);
     ma.f = p.c[sm.c[sm.forcing]]; ma.sf = p.sc[sm.c[sm.forcing]];
-    ma.rowf = (const double *)ws->d_rowf; ma.rw = pl.pm_rw; ma.irok = pl.pm_irok;
+    ma.rowf = (const double *)ws->d_rowf; ma.rw = pipe_rec_shape(p.kind).rw; ma.irok = pipe_rec_shape(p.kind).irok;
     ma.yc = p.yc; ma.xc = p.xc;
     ma.per = (p.BCx == XINV_BC_PERIODIC); ma.al = pl.aligned; ma.seam = pl.seam != 0;
     ma.nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
@@ -566,7 +572,7 @@ static int plan_occ(const Problem &p, const Plan &pl, hipStream_t st, int K, boo
         FusedArgs dummy; memset(&dummy, 0, sizeof dummy);
         occ = pl.nine ? 1 : 2;
         if (pl.nine) missing = xinv_launch_fused9(p.kind == KIND_GEN2D, K, pl.aligned, ext, dim3(1), st, dummy, &occ, pl.seam != 0);
-        else if (pl.pipe) missing = xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.npair, pl.pipe_fr, pl.aligned, ext, dim3(1), st, dummy, &occ, 0, pl.seam != 0, pl.fma);
+        else if (pl.pipe) missing = xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.pipe_fr, pl.aligned, ext, dim3(1), st, dummy, &occ, 0, pl.seam != 0, pl.fma);
         else missing = fused_dispatch(p.kind, pl.aligned, ext, pl.um | (pl.alias_ac ? 2u : 0u), K, dim3(1), dim3(256), st, dummy, &occ, pl.seam != 0, pl.fma, pl.pq);
     }
     if (have) *have = !missing;

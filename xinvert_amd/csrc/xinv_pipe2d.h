@@ -57,7 +57,10 @@
 #endif
 #define XINV_PIPE_LAG (XINV_PIPE_B + 5)   /* steps wavefront p+1 runs behind wavefront p */
 #define XINV_PIPE_NS 4            /* ring rows per hand-over */
-#define XINV_PIPE_UW(np) (128 * (np) - 4 * XINV_PIPE_P)   /* columns a tile owns with np column pairs per lane */
+/* columns a tile owns: a lane holds one column pair, 2 * XINV_PIPE_P halo columns a side.  (Two pairs per lane -- strips of
+   240 owned columns -- were measured slower, 45.2 against 40.0 us at 3600x1800, and so were the variants that stream
+   coefficient arrays as vectors, profiles/r03_pipe_vector_streams.txt: neither is built.) */
+#define XINV_PIPE_UW (128 - 4 * XINV_PIPE_P)
 #ifndef XINV_PIPE_PF0
 #define XINV_PIPE_PF0 4           /* rows in flight from HBM, wavefront 0 (S and F) */
 #endif
@@ -72,20 +75,18 @@
 #define XINV_PIPE_ST_AUX 16
 #endif
 
-// What a row needs besides S and the vector streams: one record per row, read through the scalar unit --
-// the values of the coefficient streams that are constant along x (bit q of UM), in stream order, then, when the
-// model's denominator is x-uniform (M::hoist<UM>()), the row's relaxation factor and the row part of the update
-// predicate (all ones / zero).  The predicate word is there for k_pipe_masks, which folds it into the table of update
-// masks; the march takes the masks and does not use the word (dropping it would shrink no record: 3 -> 4, 6 -> 8 doubles).
-// Padded to 4 or 8 doubles.  Standard form, A and C per row: {A[j], C[j], rq, rok}; general form, A C D E F per row:
-// {A, C, D, E, F, rq, rok, -}; general form, D E F per row (A, C, G streamed): {D, E, F, -}; no record when
-// nothing is uniform.
+// What a row needs besides S and the forcing: one record per row, read through the scalar unit -- the values of the
+// coefficient streams, all constant along x (bit q of UM), in stream order, then the row's relaxation factor and the row
+// part of the update predicate (all ones / zero).  The predicate word is there for k_pipe_masks, which folds it into the
+// table of update masks; the march takes the masks and does not use the word (dropping it would shrink no record: 3 -> 4,
+// 6 -> 8 doubles).  Padded to 4 or 8 doubles.  Standard form, A and C per row: {A[j], C[j], rq, rok}; general form,
+// A C D E F per row: {A, C, D, E, F, rq, rok, -}.
 template <class M, unsigned UM> struct PipeRec {
+    static_assert(M::template hoist<UM>(), "k_pipe2d: the model's denominator is x-uniform (the factor is a per-row value)");
     static constexpr int NCO = M::NC - 1;                                    // coefficient streams (the forcing is last)
     static constexpr int NUNI = __builtin_popcount(UM & ((1u << NCO) - 1u));
-    static constexpr bool HOIST = M::template hoist<UM>();
-    static constexpr int NW = NUNI + (HOIST ? 2 : 0);
-    static constexpr int RW = NW == 0 ? 0 : (NW <= 4 ? 4 : 8);
+    static constexpr int NW = NUNI + 2;                                      // the row predicate is word NW - 1
+    static constexpr int RW = NW <= 4 ? 4 : 8;
 };
 
 struct RowFactorArgs {
@@ -94,7 +95,7 @@ struct RowFactorArgs {
     int64_t yc, xc;
     int gen;                      // 0: standard form, 1: general form
     unsigned um;                  // which streams are per-row values
-    int hoist, rw;                // record carries rq / rok; doubles per record
+    int rw;                       // doubles per record
     XinvScal sc_;
     double *rowf;                 // [nbatch][yc][rw]
 };
@@ -120,27 +121,25 @@ __global__ __launch_bounds__(256) void k_row_factor(RowFactorArgs a)
         v[q] = 0.0;
         if ((a.um >> q) & 1u) { v[q] = a.c[q][m * a.sc[q] + j * a.xc]; f[k++] = v[q]; def = def && (v[q] != u); }
     }
-    if (a.hoist) {
-        double rq = 0.0, rok = 0.0;
-        if (inner) {
-            if (!a.gen) {
-                const double aP = a.c[0][m * a.sc[0] + (j + 1) * a.xc], a0 = v[0], c = v[1];
-                rq = a.sc_.optArg / ((aP + a0) * a.sc_.ratioSqr + (c + c));
-                rok = (def && (aP != u)) ? ones : 0.0;
-            } else {
-                const double A = v[0], C = v[1], F = v[4];
-                rq = a.sc_.optArg / ((A * a.sc_.ratioSqr + C) * 2.0
-                                     - F * a.sc_.delxSqr);
-                rok = def ? ones : 0.0;
-            }
+    double rq = 0.0, rok = 0.0;
+    if (inner) {
+        if (!a.gen) {
+            const double aP = a.c[0][m * a.sc[0] + (j + 1) * a.xc], a0 = v[0], c = v[1];
+            rq = a.sc_.optArg / ((aP + a0) * a.sc_.ratioSqr + (c + c));
+            rok = (def && (aP != u)) ? ones : 0.0;
+        } else {
+            const double A = v[0], C = v[1], F = v[4];
+            rq = a.sc_.optArg / ((A * a.sc_.ratioSqr + C) * 2.0
+                                 - F * a.sc_.delxSqr);
+            rok = def ? ones : 0.0;
         }
-        f[k++] = rq; f[k++] = rok;
     }
+    f[k++] = rq; f[k++] = rok;
     for (; k < a.rw; k++) f[k] = 0.0;
 }
 #endif
 
-// The update predicate of the hoisted march is fixed for the life of a plan -- (column may be updated) & (row may be
+// The update predicate of the march is fixed for the life of a plan -- (column may be updated) & (row may be
 // updated: the record's predicate word) & (forcing defined: its mask may not change under a plan) -- so it is
 // evaluated ONCE, into a table of lane masks (xinv_tiles.h: xinv_pipe_mask_index), and the march reads two scalar words
 // per row instead of comparing the forcing with undef in every half-sweep.
@@ -163,7 +162,7 @@ __global__ __launch_bounds__(256) void k_pipe_masks(PipeMaskArgs a)
     const int lane = threadIdx.x & 63, strip = blockIdx.y;
     const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), m = a.member0 + blockIdx.z;
     if (j >= a.yc) return;
-    const int UW = a.seam ? xinv_ring_uw(a.xc, H) : XINV_PIPE_UW(1), HW = a.seam ? xinv_ring_hw(a.xc, H, strip) : H;
+    const int UW = a.seam ? xinv_ring_uw(a.xc, H) : XINV_PIPE_UW, HW = a.seam ? xinv_ring_hw(a.xc, H, strip) : H;
     const int64_t xu0 = (int64_t)strip * UW;
     RingSeam rs = {0ull, false};
     const LaneCols lc = a.seam ? make_lanecols_ring(xu0, HW, UW, lane, a.xc, rs)
@@ -237,7 +236,7 @@ typedef xinv_v2d __attribute__((address_space(1))) *xinv_gd2ptr;
 typedef double __attribute__((address_space(1))) *xinv_gdptr;
 
 // 'extend' pre-pass for one boundary row held in the window (numbas.py:284-310), as fused_extend_fix but with
-// the value of column c0-1 of the inner row handed in (with two column pairs per lane it is the lane's own)
+// the value of column c0-1 of the inner row handed in (the march has fetched it from the lane below already)
 __device__ __forceinline__ void pipe_extend_fix(double2 &edge, const double2 &inner, double inner_w,
                                                 const LaneCols &lc, bool tall, double u)
 {
@@ -255,10 +254,7 @@ __device__ __forceinline__ void pipe_extend_fix(double2 &edge, const double2 &in
 }
 
 // one wavefront of the pipeline: sweep PW+1 on the rows of the tile [yu0, yu1).
-// A lane holds NP adjacent column pairs (NP = 2: four consecutive columns, strips of 256 columns of which 240
-// are owned): the inner neighbours of a point are then the lane's own registers and only one operand per PAIR
-// of updates crosses lanes (DPP), the row bookkeeping, the barriers and the scalar work are shared by twice the
-// arithmetic, and the column halo weighs 1.07 instead of 1.14.
+// A lane holds one column pair: one neighbour of a point is the lane's own register, the other crosses lanes (DPP).
 // Registers: ONE ring of R = PF + 4 row records (S, F, per-row factors).  Row r is loaded straight into
 // record r mod R, PF steps before it enters the window (the per-row factors two steps before), and stays
 // there until it has left the window four steps later; the march is unrolled R steps, so every record index
@@ -274,19 +270,19 @@ __device__ __forceinline__ void pipe_extend_fix(double2 &edge, const double2 &in
 // whose .x slot holds column xc-1; the half-sweeps that update the .x slots leave them out of their pass and run one more
 // pass for them alone (east operand: the next lane's .x, the new column 0), after which the phantom column mirrors
 // column xc-1 again.  Only the tiles that hold a seam lane are marched with SEAM = true (k_pipe2d below).
-template <class M, unsigned UM, bool FR, int NP, bool AL, bool EXT, int PW, int PF, bool SEAM = false>
+template <class M, unsigned UM, bool FR, bool AL, bool EXT, int PW, int PF, bool SEAM = false>
 __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, int strip, int yu0, int yu1,
-                                               const LaneCols (&lc)[NP], const int64_t (&st0)[NP], int lane,
-                                               double2 (*ring)[XINV_PIPE_NS][NP * (FR ? 2 : 1)][XINV_WAVE], int gtot,
+                                               const LaneCols (&lc)[1], const int64_t (&st0)[1], int lane,
+                                               double2 (*ring)[XINV_PIPE_NS][FR ? 2 : 1][XINV_WAVE], int gtot,
                                                double &acc, int &cnt,
                                                unsigned long long seam_lanes = 0ull)
 {
     constexpr int P = XINV_PIPE_P, H = 2 * P, D = 4, LAG = XINV_PIPE_LAG, B = XINV_PIPE_B;
+    constexpr int NP = 1;                                // column pairs per lane: what the one-trip loops below run over
     constexpr int R = PF + D;                            // row records; also the unroll period
     constexpr int PFR = M::PIPE_PFR;                     // steps the per-row record is requested ahead
     using REC = PipeRec<M, UM>;
     constexpr int NC = M::NC, FQ = M::NC - 1, RW = REC::RW;
-    constexpr bool HOIST = REC::HOIST;
     constexpr int RS = FR ? 2 : 1;                       // ring entries per column pair: S (, forcing)
     static_assert(R % D == 0 && R % B == 0 && R % XINV_PIPE_NS == 0,
                   "the unroll period must keep row parity, ring slots and barriers compile-time");
@@ -323,9 +319,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
         ownx[q] = __builtin_amdgcn_ballot_w64(lc[q].use_x); owny[q] = __builtin_amdgcn_ballot_w64(lc[q].use_y);
         nsx[q] = nsy[q] = 0.0; nnx[q] = nny[q] = 0;
     }
-    static_assert(NP == 1 || !PipeRec<M, UM>::HOIST, "the table of update masks holds one column pair per lane");
-    static_assert(!SEAM || (NP == 1 && !AL && PipeRec<M, UM>::HOIST),
-                  "seam variants: one column pair per lane, per-row records, updates under EXEC masks");
+    static_assert(!SEAM || !AL, "seam variants: unaligned strips");
 
     // the schedule (xinv_tiles.h): the first row marched -- `front` padded rows above the first one needed -- and the last
     // row needed; the march runs whole periods from the one past the other
@@ -345,7 +339,7 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
 
     double2 sw[NP][R];
     CoefWin<NC, R> cw[NP];
-    unsigned long long mkx[R], mky[R];                   // the rows' update masks (HOIST: out of the plan's table)
+    unsigned long long mkx[R], mky[R];                   // the rows' update masks, out of the plan's table
 #pragma unroll
     for (int t = 0; t < R; t++) {
         mkx[t] = mky[t] = 0ull;
@@ -400,21 +394,20 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     };
     auto request_rf = [&](int, auto stag) {
         constexpr int slot = decltype(stag)::value;
-        if constexpr (RW > 0) {                          // (rows 0 and yc-1 carry rok = 0: so do the clamped ones)
-            const unsigned roff = (unsigned)min(max(nxr, 0), (ycr - 1) * (RW * 8));
-            nxr += RW * 8;
-            const xinv_cdouble_ptr pr = (xinv_cdouble_ptr)((const char __attribute__((address_space(4))) *)rowf + roff);
-            double rec[RW];
+        // (rows 0 and yc-1 carry rok = 0: so do the clamped ones)
+        const unsigned roff = (unsigned)min(max(nxr, 0), (ycr - 1) * (RW * 8));
+        nxr += RW * 8;
+        const xinv_cdouble_ptr pr = (xinv_cdouble_ptr)((const char __attribute__((address_space(4))) *)rowf + roff);
+        double rec[RW];
 #pragma unroll
-            for (int k = 0; k < RW; k++) rec[k] = pr[k];
+        for (int k = 0; k < RW; k++) rec[k] = pr[k];
 #pragma unroll
-            for (int q = 0; q < NP; q++) {
-                int k = 0;
+        for (int q = 0; q < NP; q++) {
+            int k = 0;
 #pragma unroll
-                for (int c = 0; c < NC - 1; c++)
-                    if ((UM >> c) & 1u) cw[q].s[c][slot] = rec[k++];
-                if (HOIST) cw[q].rq[slot] = rec[k];      // (rec[k + 1], the row predicate, is in the masks)
-            }
+            for (int c = 0; c < NC - 1; c++)
+                if ((UM >> c) & 1u) cw[q].s[c][slot] = rec[k++];
+            cw[q].rq[slot] = rec[k];                     // (rec[k + 1], the row predicate, is in the masks)
         }
     };
     // the masks of row r, asked for when the row enters -- one step before its first update: the barrier's lgkmcnt(0)
@@ -422,12 +415,10 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     // s_load_dwordx4, the row clamped like the record's (rows 0 and yc-1 hold zero words)
     auto request_mask = [&](auto stag) {
         constexpr int slot = decltype(stag)::value;
-        if constexpr (HOIST) {
-            const unsigned moff = (unsigned)min(max(nxm, 0), (ycr - 1) * (XINV_PIPE_MASK_WORDS * 8));
-            nxm += XINV_PIPE_MASK_WORDS * 8;
-            const xinv_v2ull w = *(xinv_cmask_ptr)((const char __attribute__((address_space(4))) *)maskp + moff);
-            mkx[slot] = w.x; mky[slot] = w.y;
-        }
+        const unsigned moff = (unsigned)min(max(nxm, 0), (ycr - 1) * (XINV_PIPE_MASK_WORDS * 8));
+        nxm += XINV_PIPE_MASK_WORDS * 8;
+        const xinv_v2ull w = *(xinv_cmask_ptr)((const char __attribute__((address_space(4))) *)maskp + moff);
+        mkx[slot] = w.x; mky[slot] = w.y;
     };
     // (in row order, as in the loop: the vmcnt waits of the loop are computed against the worst path into it)
     xinv_unroll_steps([&](auto ttag) { request(in_lo + decltype(ttag)::value, ttag); asm volatile("" ::: "memory"); },
@@ -454,19 +445,14 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
             // the increment, added under the update predicate as EXEC (xinv_add_where: no select on the VALU)
             const double t = M::template inc<X, UM, R, false>(cw[q], sj, sjp, comp<X>(sw[q][sj]), comp<X>(sw[q][sjp]),
                                               comp<X>(sw[q][sjm]), w, e, a.sc_);
-            if constexpr (HOIST) {
-                // the predicate -- (column may be updated) & (row may be updated) & (forcing defined) -- is the row's word
-                // of the plan's table (k_pipe_masks); the seam tiles split the .x word between their two passes
-                unsigned long long rm = X ? mky[sj] : mkx[sj];
-                if constexpr (SEAM && X == 0) rm = FIX ? (rm & seam_lanes) : (rm & ~seam_lanes);
-                if constexpr (ModelFma<M>::value)          // (t is the bracket before the relaxation factor: one fma finishes)
-                    nv[q] = xinv_fma_where(comp<X>(sw[q][sj]), t, cw[q].rq[sj], rm);
-                else
-                    nv[q] = xinv_add_where(comp<X>(sw[q][sj]), t, rm);
-            } else {
-                const unsigned long long pm = __builtin_amdgcn_ballot_w64((X ? cw[q].my[sj] : cw[q].mx[sj]) != 0u);
-                nv[q] = xinv_add_where(comp<X>(sw[q][sj]), t, pm);
-            }
+            // the predicate -- (column may be updated) & (row may be updated) & (forcing defined) -- is the row's word
+            // of the plan's table (k_pipe_masks); the seam tiles split the .x word between their two passes
+            unsigned long long rm = X ? mky[sj] : mkx[sj];
+            if constexpr (SEAM && X == 0) rm = FIX ? (rm & seam_lanes) : (rm & ~seam_lanes);
+            if constexpr (ModelFma<M>::value)              // (t is the bracket before the relaxation factor: one fma finishes)
+                nv[q] = xinv_fma_where(comp<X>(sw[q][sj]), t, cw[q].rq[sj], rm);
+            else
+                nv[q] = xinv_add_where(comp<X>(sw[q][sj]), t, rm);
         }
 #pragma unroll
         for (int q = 0; q < NP; q++) setc<X>(sw[q][sj], nv[q]);
@@ -523,12 +509,6 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
                     sw[q][(U + 1) % R] = RING(PW - 1, RSLOT(-1))[q * RS][lane];   // row r+1: written B+1 steps ago
                     if (FR) cw[q].v[FQ][(U + 1) % R] = RING(PW - 1, RSLOT(-1))[q * RS + 1][lane];
                 }
-            }
-            if constexpr (!HOIST) {          // coefficient arrays that vary along x: the model's own predicate
-                const bool rv = (r - 1 >= 1) && (r - 1 <= ycr - 2);
-#pragma unroll
-                for (int q = 0; q < NP; q++)
-                    M::template derive<UM, R, false>(cw[q], SLOT(0), SLOT(1), rv && lc[q].ok_x, rv && lc[q].ok_y, a.sc_);
             }
             {   // red half-sweep on row r-1
                 const int ja = r - 1;
@@ -608,11 +588,12 @@ __device__ __forceinline__ void xinv_pipe_wave(const FusedArgs &a, int64_t m, in
     cnt += nn;                                           // SCOUNT: wave-uniform; else this lane's
 }
 
-template <class M, unsigned UM, bool FR, int NP, bool AL, bool EXT, bool SEAM = false>
+template <class M, unsigned UM, bool FR, bool AL, bool EXT, bool SEAM = false>
 __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
 {
     xinv_fresh_scalar_cache();
     constexpr int P = XINV_PIPE_P, K = P, H = 2 * K, LAG = XINV_PIPE_LAG, B = XINV_PIPE_B;
+    constexpr int NP = 1;                                // column pairs per lane
     __shared__ double2 ring[P - 1][XINV_PIPE_NS][NP * (FR ? 2 : 1)][XINV_WAVE];
 
     unsigned tag;
@@ -659,7 +640,7 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
         yu1 = (rb + 1 == a.nrb) ? (int)yc : (int)((((int64_t)(rb + 1) * yc) / a.nrb) & ~(int64_t)1);
     }
     // (SEAM: the ring layout's strips and halos, xinv_tiles.h)
-    const int UW = SEAM ? xinv_ring_uw(xc, H) : XINV_PIPE_UW(NP), HW = SEAM ? xinv_ring_hw(xc, H, strip) : H;
+    const int UW = SEAM ? xinv_ring_uw(xc, H) : XINV_PIPE_UW, HW = SEAM ? xinv_ring_hw(xc, H, strip) : H;
     const int64_t xu0 = (int64_t)strip * UW;
     LaneCols lc[NP];
     int64_t st0[NP];
@@ -667,7 +648,7 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
 #pragma unroll
     for (int q = 0; q < NP; q++) {
         if constexpr (SEAM) lc[q] = make_lanecols_ring(xu0, HW, UW, lane, xc, rs);
-        else lc[q] = make_lanecols<AL>(xu0, H, UW, lane, xc, a.per != 0, NP, q);
+        else lc[q] = make_lanecols<AL>(xu0, H, UW, lane, xc, a.per != 0);
         st0[q] = xu0 - HW + 2 * NP * lane + 2 * q;       // unwrapped store column of the pair's .x
     }
 
@@ -680,10 +661,10 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
         const bool wraps = rs.any;
 #define XINV_PIPE_MARCH(SM) \
         switch (pwi) { \
-        case 0: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 0, XINV_PIPE_PF0, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        case 1: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 1, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        case 2: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 2, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
-        default: xinv_pipe_wave<M, UM, FR, NP, AL, EXT, 3, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 0: xinv_pipe_wave<M, UM, FR, AL, EXT, 0, XINV_PIPE_PF0, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 1: xinv_pipe_wave<M, UM, FR, AL, EXT, 1, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        case 2: xinv_pipe_wave<M, UM, FR, AL, EXT, 2, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
+        default: xinv_pipe_wave<M, UM, FR, AL, EXT, 3, XINV_PIPE_PF, SM>(a, m, strip, yu0, yu1, lc, st0, lane, ring, gtot, acc, cnt, rs.lanes); break; \
         }
         if (wraps) { XINV_PIPE_MARCH(SEAM) } else { XINV_PIPE_MARCH(false) }
 #undef XINV_PIPE_MARCH

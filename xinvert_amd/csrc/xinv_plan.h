@@ -259,7 +259,7 @@ static int plan5_xuniform(const Problem &p, const xinv_options &opt, Workspace *
         if (p.kind != KIND_STD2DT && opt.rows_per_tile == 0 && opt.sweeps_per_launch == 0 &&
             !(opt.flags & (XINV_FLAG_NO_TILE_SKIP | XINV_FLAG_NO_PIPE)) && p.nbatch <= 64 &&
             p.nbatch * p.yc * p.xc >= (int64_t)2000000) {
-            const int uw_pipe = pl.seam ? xinv_ring_uw(p.xc, 2 * XINV_PIPE_P) : XINV_PIPE_UW(1);   // (one column pair per lane: what ships)
+            const int uw_pipe = pl.seam ? xinv_ring_uw(p.xc, 2 * XINV_PIPE_P) : XINV_PIPE_UW;
             if (p.xc >= uw_pipe && p.nbatch * cdiv(p.xc, uw_pipe) * (p.yc + 1) <= (int64_t)50000000) {
                 const int rc = issue_strip_active(p, ws, st, uw_pipe, sm.c[sm.forcing]);
                 if (rc) return rc;
@@ -328,14 +328,11 @@ static int plan5_sweeps(const Problem &p, const xinv_options &opt, Workspace *, 
     }
     pl.pipe = pipe_want && pl.K == XINV_PIPE_P;
     pl.tpw = pl.pipe ? 1 : 4;
-    // one column pair per lane (two -- strips of 240 owned columns -- were measured slower, 45.2 against 40.0 us at
-    // 3600x1800, and are no longer instantiated: round 5)
-    pl.npair = 1;
     // the forcing through the LDS ring where the launch's streams (S read + write + forcing, every member) no
     // longer fit the caches and the later wavefronts' forcing requests would go back to HBM; XINV_PIPE_FR=0|1 forces
     const int fr_env = opt.pipe_fr ? (opt.pipe_fr > 0 ? 1 : 0) : XINV_ENV_INT("XINV_PIPE_FR", -1);
     const bool fr_size = (double)p.nbatch * (double)p.yc * (double)p.xc * 24.0 > 2.0e8;
-    pl.pipe_fr = pl.pipe && pipe_form && pl.npair == 1 && (fr_env < 0 ? fr_size : fr_env != 0);
+    pl.pipe_fr = pl.pipe && (fr_env < 0 ? fr_size : fr_env != 0);
     return XINV_OK;
 }
 
@@ -366,31 +363,25 @@ static int plan5_point_factor(const Problem &p, const xinv_options &opt, Workspa
     return XINV_OK;
 }
 
-// the pipelined pass's per-row records of the x-uniform streams (+ relaxation factor and row predicate when the model hoists)
+// the pipelined pass's per-row records (the x-uniform streams, the relaxation factor, the row predicate) and its update masks
 static int plan5_row_records(const Problem &p, const xinv_options &, Workspace *ws, hipStream_t st, Plan &pl)
 {
     if (!pl.pipe) return XINV_OK;
     const StreamMap &sm = stream_map(p.kind);
-    const bool gen = (p.kind == KIND_GEN2D);
-    const bool hoist = gen ? ((pl.um & 0x13u) == 0x13u) : ((pl.um & 3u) == 3u);
-    const int nw = __builtin_popcount(pl.um & ((1u << sm.nuni) - 1u)) + (hoist ? 2 : 0);
-    const int rw = nw == 0 ? 0 : (nw <= 4 ? 4 : 8);
-    if (!rw) return XINV_OK;
+    const int rw = pipe_rec_shape(p.kind).rw;
     const int rc = ensure_dev(&ws->d_rowf, &ws->d_rowf_cap, (size_t)p.nbatch * p.yc * rw * sizeof(double));
     if (rc) return rc;
     RowFactorArgs ra;
     memset(&ra, 0, sizeof ra);
     for (int q = 0; q < sm.nuni; q++) { ra.c[q] = p.c[sm.c[q]]; ra.sc[q] = p.sc[sm.c[q]]; }      // A, C (, D, E, F)
-    ra.gen = gen ? 1 : 0; ra.um = pl.um; ra.hoist = hoist ? 1 : 0; ra.rw = rw;
+    ra.gen = p.kind == KIND_GEN2D; ra.um = pl.um; ra.rw = rw;
     ra.yc = p.yc; ra.xc = p.xc; ra.sc_ = p.sc_; ra.rowf = (double *)ws->d_rowf;
     hipLaunchKernelGGL(k_row_factor, dim3(cdiv(p.yc, 256), (unsigned)p.nbatch, 1), dim3(256), 0, st, ra);
-    if (!hoist) return XINV_OK;
-    // the hoisted march's update masks: the row predicate just written, the launch's lane -> column map, the forcing's mask
+    // the march's update masks: the row predicate just written, the launch's lane -> column map, the forcing's mask
     const int nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
     const int rc2 = ensure_dev(&ws->d_pmask, &ws->d_pmask_cap,
                                (size_t)xinv_pipe_mask_count(p.nbatch, nstrip, p.yc) * sizeof(unsigned long long));
     if (rc2) return rc2;
-    pl.pmask = true; pl.pm_rw = rw; pl.pm_irok = nw - 1;
     if (p.masks_by_chunk) return XINV_OK;                // (the forcing of the later chunks is not there yet: roll_join)
     return launch_pipe_masks(p, pl, ws, st, 0, p.nbatch);
 }

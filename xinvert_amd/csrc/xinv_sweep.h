@@ -131,7 +131,7 @@ static void plan_stats(const Problem &p, const Plan &pl, int lanes, int64_t laun
     t_stats.xuniform_mask = (fused || p.kind == KIND_BIH2D) ? (int32_t)pl.um : 0;
     t_stats.masked_tile_pct = (fused && pl.skip) ? pl.skip_pct : 0;
     t_stats.masked_tile_ppm = (fused && pl.skip) ? pl.skip_ppm : 0;
-    t_stats.pipelined = (fused && pl.pipe) ? pl.npair : 0;
+    t_stats.pipelined = (fused && pl.pipe) ? 1 : 0;
     t_stats.lanes = lanes;
     t_stats.point_factor = (fused && pl.pq) ? (pl.alias_ac ? 2 : 1) : 0;
     if (fused && p.kind == KIND_BIH2D) t_stats.point_factor = pl.bih_vm;
