@@ -13,42 +13,14 @@ import pytest
 import fourier_model as M
 import resid_model as RM
 import xinvert_amd as xa
+from fourier_ld import dft_longdouble, err_ld
 from xinvert_amd import _lib, fourier, synthetic
 
 pytestmark = pytest.mark.gpu
 U = -9.99e8
-LD = np.longdouble
 
 
 # ------------------------------------------------------------------ the row transform
-_WLD = {}
-
-
-def dft_longdouble(x):
-    """The half spectrum of real rows [rows, n] by the O(n^2) sum in long double, exp(-2 pi i t / n) tabulated once per n."""
-    n = x.shape[-1]
-    if n not in _WLD:
-        ang = LD(2) * LD('3.14159265358979323846264338327950288') * np.arange(n, dtype=LD) / LD(n)
-        _WLD[n] = (np.cos(ang), -np.sin(ang))
-    wr, wi = _WLD[n]
-    xl = x.astype(LD)
-    K = n // 2 + 1
-    out_r, out_i = np.empty((x.shape[0], K), dtype=LD), np.empty((x.shape[0], K), dtype=LD)
-    i = np.arange(n)
-    for k0 in range(0, K, 64):                             # (in blocks of wavenumbers: the table index is (i k) mod n)
-        k = np.arange(k0, min(K, k0 + 64))
-        t = (i[None, :] * k[:, None]) % n
-        out_r[:, k] = xl @ wr[t].T
-        out_i[:, k] = xl @ wi[t].T
-    return out_r, out_i
-
-
-def err_ld(X, truth):
-    tr, ti = truth
-    dr, di = X.real.astype(LD) - tr, X.imag.astype(LD) - ti
-    return float(np.sqrt((dr * dr + di * di).sum()) / np.sqrt((tr * tr + ti * ti).sum()))
-
-
 def rel(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
