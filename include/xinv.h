@@ -492,6 +492,26 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
  * ignores the imaginary parts of X[0] and X[n/2] and divides by n).  inverse = 0: in real, out spectrum; 1: the reverse.
  * Not in place.  Device pointers; only queued on `stream`.
  *   xinv_rowdft_f64_dev(out, in, nrows, n, inverse, stream)
+ * Plans -- one operator, many forcings (time stepping, ensembles, restarts).  The factorisation of the K systems,
+ * inv_j = 1 / (di_jk - lo_j gamma_{j-1}) and gamma_j = up_j inv_j, depends on A, C, ratioSqr and xc alone.  create copies
+ * A and C (device pointers, one value per row; strides[2] of A and C, 0 = shared, else >= yc), refuses `undef` on A rows
+ * 1 .. yc-1 and C rows 1 .. yc-2 (XINV_ERR_ARG naming the member; it waits on the host), computes the factors once
+ * (16 bytes per coefficient set, row and wavenumber: one set when A and C are both shared) and allocates the plan's own
+ * spectrum (16 bytes per member, row and wavenumber) and status words.  solve ONLY QUEUES on `stream`: the undef check
+ * of F and of rows 0 and yc-1 of S, the forward transforms, a substitution without a division (the real and imaginary
+ * parts are independent recurrences: 2K lanes per member), the inverse transform, the status words to a pinned mirror,
+ * the plan's event.  No host wait, no workspace lock, no allocation; xinv_last_stats is not updated.  sS, sF: member
+ * strides of S and F in elements, sF = 0 = one forcing for every member.  The results are bitwise the one-shot entry's.
+ * UNLIKE the one-shot entry, a member that holds `undef` at a point the solve reads keeps its S UNTOUCHED while the other
+ * members ARE solved.  A solve on another stream is ordered behind the plan's previous solve (the spectrum is the
+ * plan's); two plans are independent.  status waits for the plan's last solve, fills flags[m] = {overflow, 0, 0} (host
+ * double[nbatch][3]) and bad[m] = the member's undef count (host int[nbatch], or NULL), then returns XINV_ERR_ARG naming
+ * the first member with bad[m] != 0.  destroy waits for the last solve and frees what the plan owns.  Not for stream
+ * capture.
+ *   xinv_fourier_plan_create_standard_2d_f64_dev(&plan, A, C, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, stream)
+ *   xinv_fourier_plan_solve_f64_dev(plan, S, F, sS, sF, stream)
+ *   xinv_fourier_plan_status(plan, flags, bad)
+ *   xinv_fourier_plan_destroy(plan)
  * The prototypes live in a header of their own, which this one includes: a caller of xinv.h has them. */
 #include "xinv_fourier.h"
 

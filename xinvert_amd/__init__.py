@@ -12,7 +12,8 @@ Layout (only what the hot path needs):
   finitediffs.py FiniteDiff / deriv / deriv2 / padBCs: one HIP launch per operator (reference xinvert/finitediffs.py)
   utils.py       loop_noncore (reference xinvert/utils.py)
   tridiag.py     trace / traceCyclic: batched tridiagonal direct solves, one system per lane (reference xinvert/numbas.py)
-  fourier.py     rfft_rows / irfft_rows, and the eligibility test of iParams['method'] = 'fourier' (the direct 2-D solve)
+  fourier.py     rfft_rows / irfft_rows, the eligibility test of iParams['method'] = 'fourier' (the direct 2-D solve), and
+                 FourierPlan: the factors of one operator kept across solves
   multigrid.py   invert_MultiGrid: coarse-to-fine SOR solves, HIP restriction / prolongation (reference xinvert/apps.py)
 """
 from .field import Field                                           # noqa: F401
@@ -28,6 +29,6 @@ from .utils import loop_noncore                                    # noqa: F401
 from .finitediffs import FiniteDiff, deriv, deriv2, padBCs, DeviceField   # noqa: F401
 from .multigrid import invert_MultiGrid                             # noqa: F401
 from .tridiag import trace, traceCyclic                             # noqa: F401
-from .fourier import rfft_rows, irfft_rows                          # noqa: F401
+from .fourier import rfft_rows, irfft_rows, FourierPlan             # noqa: F401
 
 __version__ = '0.1.0'

@@ -81,6 +81,8 @@ EXPORTS = [
     'xinv_residual_standard_3d_f64_dev', 'xinv_residual_standard_3d_f64_batched',
     'xinv_residual_general_3d_f64_dev', 'xinv_residual_general_3d_f64_batched',
     'xinv_fourier_standard_2d_f64_dev', 'xinv_fourier_standard_2d_f64_batched', 'xinv_rowdft_f64_dev',
+    'xinv_fourier_plan_create_standard_2d_f64_dev', 'xinv_fourier_plan_solve_f64_dev', 'xinv_fourier_plan_status',
+    'xinv_fourier_plan_destroy',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -138,6 +140,12 @@ def load():
     L.xinv_fourier_standard_2d_f64_dev.argtypes = [_vp] * 4 + four_tail + [_vp]
     L.xinv_fourier_standard_2d_f64_batched.argtypes = [_dp] * 4 + four_tail + [_opt]
     L.xinv_rowdft_f64_dev.argtypes = [_vp, _vp, _i64, _i64, _int, _vp]
+    # its plans: create(&plan, A, C, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, stream); solve(plan, S, F, sS, sF,
+    # stream); status(plan, flags (host), bad (host int32 or NULL)); destroy(plan)
+    L.xinv_fourier_plan_create_standard_2d_f64_dev.argtypes = [_pvp, _vp, _vp, _i64, _ip, _i64, _i64, _f64, _f64, _f64, _vp]
+    L.xinv_fourier_plan_solve_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp]
+    L.xinv_fourier_plan_status.argtypes = [_vp, _dp, ctypes.POINTER(ctypes.c_int)]
+    L.xinv_fourier_plan_destroy.argtypes = [_vp]
     L.xinv_plan_solve_f64_dev.argtypes = [_vp, _vp, _dp, _i64, _f64, _vp]
     L.xinv_plan_solve_frames_f64_dev.argtypes = [_vp, _vp, _vp, _i64, _i64, _dp, _i64, _f64, _vp]
     L.xinv_plan_refresh.argtypes = [_vp, _vp]

@@ -22,6 +22,13 @@
 //                       per row.  The forward factors up_j / beta_j sit in the workspace; the right-hand sides are replaced in
 //                       place by the forward result and then by the solution.  A non-finite solution sets the member's word.
 //   k_fourier_check     counts `undef` among the points the solve reads; runs before anything is written.
+// Two more for a plan (xinv_fourier_plan_*: one operator, many forcings), which keeps what depends on A, C, ratioSqr and xc alone:
+//   k_fourier_factor    one wavenumber per lane and coefficient set, once per plan: k_fourier_tri's march without the
+//                       right-hand sides, storing inv_j = 1 / beta_j and gamma_j = up_j inv_j -- the same expressions, the same bits.
+//   k_fourier_subst     one lane per (wavenumber, real or imaginary part): the two parts are independent real recurrences
+//                       with the same factors, so a member offers 2K lanes.  Forward rho_j = (r_j - lo_j rho_{j-1}) inv_j,
+//                       backward x_j = rho_j - gamma_j x_{j+1}: no division; rows are loaded a batch ahead of the chain.
+// and k_rowdft takes a per-member skip word (the plan's undef counts): a member that holds `undef` keeps its S.
 // Rules of DESIGN 4.9: 64-bit indexing, solver data and tables through vector loads only, no floating-point atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +40,9 @@
 #define XINV_DFT_MAX_PASS 12             /* 4096 = 4^6; 3^7 = 2187: seven passes at the most */
 #define XINV_FTRI_WG 64                  /* k_fourier_tri: one wavefront per workgroup, one wavenumber per lane */
 #define XINV_FCHK_WG 256
+#define XINV_FFAC_WG 64                  /* k_fourier_factor: as k_fourier_tri */
+#define XINV_FSUB_WG 64                  /* k_fourier_subst: one wavefront per workgroup, 2K lanes per member */
+#define XINV_FSUB_AHEAD 8                /* ... rows loaded ahead of the dependent chain */
 
 // Which rows a k_rowdft launch transforms and where they go: nrows / rpm members of rpm rows each, a workgroup per pair of
 // rows (2p, 2p + 1) of ONE member (an odd rpm leaves the last row alone).  Row q of member m: real side at real +
@@ -47,6 +57,7 @@ struct RowDftArgs {
     double scale;                        // forward: applied to the real input (delxSqr; 1: exact)
     int n, npass;
     int radix[XINV_DFT_MAX_PASS];
+    const int *skip;                     // null, or [members]: a workgroup whose member's word is not 0 does nothing
 };
 
 struct FourierTriArgs {
@@ -55,6 +66,26 @@ struct FourierTriArgs {
     const double *A, *C;                 // one value per row, [nbatch or 1][yc]
     const double *lam;                   // [K]
     int64_t sA, sC;                      // member strides (0 = shared)
+    int64_t yc, K, member0;
+    double ratioSqr;
+    int *ovf;                            // [nbatch]
+};
+
+// The factors of a plan: per coefficient set (one member's A, C, or the one shared pair) two planes [yc][K], inv then gamma.
+struct FourierFactorArgs {
+    double *fac;                         // [nset][2][yc][K]; rows 0 and yc-1 are not written
+    const double *A, *C;                 // one value per row, [nset or 1][yc]
+    const double *lam;                   // [K]
+    int64_t sA, sC;                      // set strides (0 = shared)
+    int64_t yc, K, set0;
+    double ratioSqr;
+};
+
+struct FourierSubstArgs {
+    double *spec;                        // [nbatch][yc][2K] doubles: as FourierTriArgs::spec
+    const double *fac;                   // FourierFactorArgs::fac
+    const double *A;                     // the plan's copy, [nbatch or 1][yc]: lo_j = A[j] ratioSqr
+    int64_t sA, sfac;                    // member strides of A and of fac (0 = shared)
     int64_t yc, K, member0;
     double ratioSqr;
     int *ovf;                            // [nbatch]
@@ -135,9 +166,12 @@ __global__ void __launch_bounds__(XINV_DFT_WG) k_rowdft(RowDftArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char xinv_dft_lds[];
     const int n = a.n, K = n / 2 + 1, tid = threadIdx.x;
-    xinv_c2 *buf0 = (xinv_c2 *)xinv_dft_lds, *buf1 = buf0 + n;
     // a pair never straddles two members: a non-finite row spoils its partner, and must not leave its member
     const int64_t ppm = (a.rpm + 1) / 2, m0 = (int64_t)blockIdx.x / ppm, q0 = 2 * ((int64_t)blockIdx.x % ppm);
+    // (the word was written by a kernel queued before this one: read through the coherent L2, never the scalar cache;
+    // uniform over the workgroup, and before LDS or a barrier is touched)
+    if (a.skip && __hip_atomic_load(a.skip + m0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+    xinv_c2 *buf0 = (xinv_c2 *)xinv_dft_lds, *buf1 = buf0 + n;
     const bool two = q0 + 1 < a.rpm;
     double *x0 = a.real + m0 * a.r_member + a.r_first + q0 * a.r_step, *x1 = x0 + (two ? a.r_step : 0);
     double *X0 = a.spec + m0 * a.s_member + a.s_first + q0 * a.s_step, *X1 = X0 + (two ? a.s_step : 0);
@@ -236,6 +270,102 @@ __global__ void __launch_bounds__(XINV_FTRI_WG) k_fourier_tri(FourierTriArgs a)
     if (bad) atomicOr(a.ovf + m, 1);
 }
 
+// grid: (ceil(K / 64), coefficient sets of the chunk).  The expressions of k_fourier_tri, operation by operation.
+__global__ void __launch_bounds__(XINV_FFAC_WG) k_fourier_factor(FourierFactorArgs a)
+{
+    const int64_t k = (int64_t)blockIdx.x * XINV_FFAC_WG + threadIdx.x, s = a.set0 + blockIdx.y;
+    if (k >= a.K) return;
+    const int64_t yc = a.yc, K = a.K;
+    double *iv = a.fac + s * 2 * yc * K + k, *gm = iv + yc * K;
+    const double *A = a.A + s * a.sA, *C = a.C + s * a.sC;
+    const double lam = a.lam[k], rs = a.ratioSqr;
+    double gp = 0.0, Aj = A[1];
+    for (int64_t j = 1; j <= yc - 2; j++) {
+        const double Ap = A[j + 1], Cj = C[j];
+        const double lo = Aj * rs, up = Ap * rs, di = -((Ap + Aj) * rs + Cj * lam);
+        const double inv = 1.0 / (j == 1 ? di : di - lo * gp);
+        gp = up * inv;
+        iv[j * K] = inv;
+        gm[j * K] = gp;
+        Aj = Ap;
+    }
+}
+
+// grid: (ceil(2K / 64), members of the chunk).  Lane q marches the double at spec[(m yc + j) 2K + q] with the factors of
+// wavenumber q >> 1.  The loads of a batch of rows do not depend on the chain: they are issued a batch ahead of it.
+__global__ void __launch_bounds__(XINV_FSUB_WG) k_fourier_subst(FourierSubstArgs a)
+{
+    const int64_t q = (int64_t)blockIdx.x * XINV_FSUB_WG + threadIdx.x, m = a.member0 + blockIdx.y;
+    const int64_t yc = a.yc, K = a.K, K2 = 2 * a.K;
+    if (q >= K2) return;
+    constexpr int U = XINV_FSUB_AHEAD;
+    double *sp = a.spec + m * yc * K2 + q;
+    const double *iv = a.fac + m * a.sfac + (q >> 1), *gm = iv + yc * K;
+    const double *A = a.A + m * a.sA;
+    const double rs = a.ratioSqr;
+
+    // forward: rows ascending; the known row 0 enters through lo_1, row yc-1 through up on row yc-2
+    const int64_t jl = yc - 2;
+    const double last = sp[(yc - 1) * K2], upl = A[yc - 1] * rs;
+    double p = sp[0];
+    // (a batch's loads are unconditional -- past the march's end they read its last row again, unused -- and nothing in
+    // the load phase uses a loaded value: no wait until the chain needs the row)
+    double r[U], f[U], la[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int64_t j = 1 + u <= jl ? 1 + u : jl;
+        r[u] = sp[j * K2]; f[u] = iv[j * K]; la[u] = A[j];
+    }
+    for (int64_t j0 = 1; j0 <= jl; j0 += U) {
+        double rn[U], fn[U], ln[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int64_t j = j0 + U + u <= jl ? j0 + U + u : jl;
+            rn[u] = sp[j * K2]; fn[u] = iv[j * K]; ln[u] = A[j];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int64_t j = j0 + u;
+            if (j <= jl) {
+                double rr = r[u];
+                if (j == jl) rr = rr - upl * last;
+                const double lo = la[u] * rs;
+                p = (rr - lo * p) * f[u];
+                sp[j * K2] = p;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) { r[u] = rn[u]; f[u] = fn[u]; la[u] = ln[u]; }
+    }
+    // backward: row yc-2 stands
+    int bad = !isfinite(p);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int64_t j = jl - 1 - u >= 1 ? jl - 1 - u : 1;
+        r[u] = sp[j * K2]; f[u] = gm[j * K];
+    }
+    for (int64_t j0 = jl - 1; j0 >= 1; j0 -= U) {
+        double rn[U], fn[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int64_t j = j0 - U - u >= 1 ? j0 - U - u : 1;
+            rn[u] = sp[j * K2]; fn[u] = gm[j * K];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int64_t j = j0 - u;
+            if (j >= 1) {
+                p = r[u] - f[u] * p;
+                sp[j * K2] = p;
+                bad |= !isfinite(p);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) { r[u] = rn[u]; f[u] = fn[u]; }
+    }
+    if (bad) atomicOr(a.ovf + m, 1);
+}
+
 // grid: (yc, members of the chunk): row j of F (1 .. yc-2) and of S (0, yc-1); thread 0 also tests A[j] (1 .. yc-1), C[j] (1 .. yc-2)
 __global__ void __launch_bounds__(XINV_FCHK_WG) k_fourier_check(FourierCheckArgs a)
 {
@@ -258,3 +388,5 @@ __global__ void __launch_bounds__(XINV_FCHK_WG) k_fourier_check(FourierCheckArgs
 __attribute__((visibility("hidden"))) int xinv_launch_rowdft(const RowDftArgs &a, bool inverse, hipStream_t st);
 __attribute__((visibility("hidden"))) void xinv_launch_fourier_tri(FourierTriArgs a, int64_t nbatch, hipStream_t st);
 __attribute__((visibility("hidden"))) void xinv_launch_fourier_check(FourierCheckArgs a, int64_t nbatch, hipStream_t st);
+__attribute__((visibility("hidden"))) void xinv_launch_fourier_factor(FourierFactorArgs a, int64_t nset, hipStream_t st);
+__attribute__((visibility("hidden"))) void xinv_launch_fourier_subst(FourierSubstArgs a, int64_t nbatch, hipStream_t st);

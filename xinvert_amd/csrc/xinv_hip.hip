@@ -549,6 +549,29 @@ int xinv_rowdft_f64_dev(double *out, const double *in, int64_t nrows, int64_t n,
     GUARD(rowdft_dev(out, in, nrows, n, inverse, (hipStream_t)stream))
 }
 
+// ... and its plans: the per-wavenumber factors once, a solve per forcing (fplan_* of xinv_fourier_host.h)
+int xinv_fourier_plan_create_standard_2d_f64_dev(xinv_fourier_plan **plan, const double *A, const double *C, int64_t nbatch,
+                                                 const int64_t *strides, int64_t yc, int64_t xc, double delxSqr,
+                                                 double ratioSqr, double undef, void *stream)
+{
+    GUARD(fplan_create(plan, A, C, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, (hipStream_t)stream))
+}
+
+int xinv_fourier_plan_solve_f64_dev(xinv_fourier_plan *plan, double *S, const double *F, int64_t sS, int64_t sF, void *stream)
+{
+    GUARD(fplan_solve(plan, S, F, sS, sF, (hipStream_t)stream))
+}
+
+int xinv_fourier_plan_status(xinv_fourier_plan *plan, double *flags, int *bad)
+{
+    GUARD(fplan_status(plan, flags, bad))
+}
+
+int xinv_fourier_plan_destroy(xinv_fourier_plan *plan)
+{
+    GUARD(fplan_destroy(plan))
+}
+
 // ---- the residual L(S) - F of the five second-order forms (k_resid2d / k_resid3d; include/xinv_resid.h) ------------
 // The solve entries' arrays and scalars behind R and S; optArg is accepted and ignored.
 int xinv_residual_standard_2d_f64_dev(double *R, const double *S, const double *A, const double *B, const double *C,

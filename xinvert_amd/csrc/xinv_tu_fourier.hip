@@ -1,4 +1,5 @@
-// xinv_tu_fourier.hip -- instantiations of k_rowdft / k_fourier_tri / k_fourier_check (the direct Fourier solve: xinv_fourier.h).
+// xinv_tu_fourier.hip -- instantiations of k_rowdft / k_fourier_tri / k_fourier_check (the direct Fourier solve: xinv_fourier.h)
+// and of a plan's k_fourier_factor / k_fourier_subst.
 #define XINV_FOURIER_KERNELS
 #include "xinv_fourier.h"
 
@@ -26,6 +27,26 @@ void xinv_launch_fourier_tri(FourierTriArgs a, int64_t nbatch, hipStream_t st)
         const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
         a.member0 = m0;
         hipLaunchKernelGGL(k_fourier_tri, dim3(gx, (unsigned)nm), dim3(XINV_FTRI_WG), 0, st, a);
+    }
+}
+
+void xinv_launch_fourier_factor(FourierFactorArgs a, int64_t nset, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((a.K + XINV_FFAC_WG - 1) / XINV_FFAC_WG);
+    for (int64_t s0 = 0; s0 < nset; s0 += FOURIER_MEMBER_CHUNK) {
+        const int64_t ns = nset - s0 < FOURIER_MEMBER_CHUNK ? nset - s0 : FOURIER_MEMBER_CHUNK;
+        a.set0 = s0;
+        hipLaunchKernelGGL(k_fourier_factor, dim3(gx, (unsigned)ns), dim3(XINV_FFAC_WG), 0, st, a);
+    }
+}
+
+void xinv_launch_fourier_subst(FourierSubstArgs a, int64_t nbatch, hipStream_t st)
+{
+    const unsigned gx = (unsigned)((2 * a.K + XINV_FSUB_WG - 1) / XINV_FSUB_WG);
+    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
+        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
+        a.member0 = m0;
+        hipLaunchKernelGGL(k_fourier_subst, dim3(gx, (unsigned)nm), dim3(XINV_FSUB_WG), 0, st, a);
     }
 }
 

@@ -1,5 +1,6 @@
 """The direct Fourier solve of the 2-D standard form for periodic x (iParams['method'] = 'fourier'; include/xinv.h,
-"fourier"): the row transform for callers who want the spectrum, and the eligibility test of the front end.
+"fourier"): the row transform for callers who want the spectrum, the eligibility test of the front end, and FourierPlan
+for callers who solve one operator again and again (the factors are kept; a solve only queues).
 
 rfft_rows / irfft_rows are numpy.fft.rfft / irfft along the last axis of a CUDA float64 tensor, on the HIP kernel k_rowdft
 (queued on the current stream).  Row lengths are products of 2, 3 and 5 up to MAX_N.  There is no CPU fallback.
@@ -72,8 +73,128 @@ def irfft_rows(X, n=None):
     return out
 
 
+class FourierPlan:
+    """One operator, many forcings (include/xinv.h, "fourier": xinv_fourier_plan_*).  The per-wavenumber factors are computed
+    once, here; every `solve` then only queues a check pass, three transforms and a substitution without a division.
+
+    A, C: numpy arrays or CUDA float64 tensors, one value per row: [yc] (shared by the batch) or [nbatch, yc].  The plan
+    keeps its own copies.  `undef` at a point of A or C the solve reads raises XinvError."""
+
+    def __init__(self, A, C, nbatch, yc, xc, delxSqr, ratioSqr, undef=-9.99e8, device=0):
+        import ctypes
+        import torch
+        self._h = None
+        self.L = _lib.require_gpu()
+        self.nbatch, self.yc, self.xc = int(nbatch), int(yc), int(xc)
+        self.dev = torch.device('cuda', device)
+        self.K = self.xc // 2 + 1
+
+        def rows(a, name):
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            a = a.to(device=self.dev, dtype=torch.float64).contiguous()
+            if tuple(a.shape) not in ((self.yc,), (self.nbatch, self.yc)):
+                raise _lib.XinvError('%s must be one value per row, [yc] or [nbatch, yc] = [%d] or [%d, %d], got %s'
+                                     % (name, self.yc, self.nbatch, self.yc, list(a.shape)))
+            return a
+
+        A, C = rows(A, 'A'), rows(C, 'C')
+        self.nset = self.nbatch if (A.ndim == 2 or C.ndim == 2) and self.nbatch > 1 else 1
+        # what the plan holds in HBM: factors, spectrum, its copies of A and C, the status words
+        self.nbytes = (16 * self.nset + 16 * self.nbatch) * self.yc * self.K + 8 * (A.numel() + C.numel()) + 8 * self.nbatch
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream(self.dev)
+            rc = self.L.xinv_fourier_plan_create_standard_2d_f64_dev(
+                ctypes.byref(h), _lib.dptr(A), _lib.dptr(C), self.nbatch,
+                _lib.strides_arg([self.yc if A.ndim == 2 else 0, self.yc if C.ndim == 2 else 0]), self.yc, self.xc,
+                float(delxSqr), float(ratioSqr), float(undef), ctypes.c_void_p(st.cuda_stream))
+        _lib.check(rc)                                       # (create returns with the copies made: A and C may go)
+        self._h = h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self):
+        """Wait for the last solve and free what the plan owns."""
+        h, self._h = getattr(self, '_h', None), None
+        if h is not None:
+            self.L.xinv_fourier_plan_destroy(h)
+
+    def _live(self):
+        if self._h is None:
+            raise _lib.XinvError('the Fourier plan has been closed')
+        return self._h
+
+    def solve(self, S, F, stream=None):
+        """Queue one solve on `stream` (default: torch's current stream): S [nbatch, yc, xc] CUDA float64, rows contiguous,
+        the members at least one slice apart; rows 0 and yc-1 are the boundary values, rows 1 .. yc-2 are overwritten.
+        F [nbatch, yc, xc], or [yc, xc]: one forcing for every member.  Nothing is waited for: `status()` has the flags."""
+        import ctypes
+        import torch
+        h = self._live()
+        nb, yc, xc = self.nbatch, self.yc, self.xc
+        for t, name in ((S, 'S'), (F, 'F')):
+            if not isinstance(t, torch.Tensor) or t.device != self.dev or t.dtype != torch.float64:
+                raise _lib.XinvError('%s must be a float64 tensor on %s' % (name, self.dev))
+        if S.ndim == 2 and nb == 1:
+            S = S.unsqueeze(0)
+        if tuple(S.shape) != (nb, yc, xc) or S.stride(2) != 1 or S.stride(1) != xc or (nb > 1 and S.stride(0) < yc * xc):
+            raise _lib.XinvError('S must be [%d, %d, %d] with contiguous slices at least one slice apart, got shape %s strides %s'
+                                 % (nb, yc, xc, list(S.shape), list(S.stride())))
+        if tuple(F.shape) == (yc, xc):
+            ok, sF = F.is_contiguous(), 0
+        else:
+            ok = tuple(F.shape) == (nb, yc, xc) and F.stride(2) == 1 and F.stride(1) == xc and (nb == 1 or F.stride(0) >= yc * xc)
+            sF = F.stride(0) if ok and nb > 1 else 0
+        if not ok:
+            raise _lib.XinvError('F must be [%d, %d, %d] or [%d, %d] with contiguous slices, got shape %s strides %s'
+                                 % (nb, yc, xc, yc, xc, list(F.shape), list(F.stride())))
+        st = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(self.L.xinv_fourier_plan_solve_f64_dev(h, _lib.dptr(S), _lib.dptr(F), S.stride(0) if nb > 1 else 0, sF,
+                                                             ctypes.c_void_p(st.cuda_stream)))
+
+    def status(self):
+        """Wait for the last solve -> (flags [nbatch, 3] = [overflow, 0, 0], bad [nbatch] = undef counts).  Raises XinvError
+        naming the first member that held `undef` at a point the solve reads (its S was left alone; the others are solved);
+        `self.flags` and `self.bad` are filled either way."""
+        import ctypes
+        h = self._live()
+        self.flags = np.zeros((self.nbatch, 3))
+        self.bad = np.zeros(self.nbatch, dtype=np.int32)
+        rc = self.L.xinv_fourier_plan_status(h, _lib.hptr(self.flags), self.bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        _lib.check(rc)
+        return self.flags, self.bad
+
+
 def _refuse(why):
     raise Exception("iParams['method'] = 'fourier': %s; 'sor' solves this case" % why)
+
+
+def resident_eligible(kind, B_nonzero, BCy, BCx, varies, yc, xc):
+    """The conditions of the Fourier path on a batch that is resident in HBM (ResidentProblem.solve_fourier), in the order and
+    words of `eligible`; `varies`: the names of the coefficient arrays among A, C that vary along x.  The undef test is the
+    device's (FourierPlan: at creation for A and C, in every solve for F and the boundary rows of S)."""
+    if kind != 'std2d':
+        raise _lib.XinvError("solve_fourier is available for the 2-D standard form only (kind 'std2d'), not for kind %r" % (kind,))
+    if B_nonzero:
+        _refuse('B must be identically zero (the array B is not)')
+    if BCy != 'fixed':
+        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCy,))
+    if BCx != 'periodic':
+        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCx,))
+    for name in ('A', 'C'):
+        if name in varies:
+            _refuse('%s must be constant along x (the array %s varies along it)' % (name, name))
+    if yc < 3:
+        _refuse('yc must be at least 3, got %d' % yc)
+    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
+    if err:
+        _refuse(err)
 
 
 def _per_row(name, a, rowconst):

@@ -44,6 +44,7 @@ class ResidentProblem:
         self.device = device
         self.use_plan = bool(plan)
         self._plans = {}
+        self._fplan = None                                   # the Fourier plan (solve_fourier), made on first use
         S0 = np.asarray(p['S0'])
         form = forms.FORMS[self.kind]
         core_nd = form.rank
@@ -102,6 +103,12 @@ class ResidentProblem:
         plans, self._plans = getattr(self, '_plans', {}), {}
         for h in plans.values():
             self.L.xinv_plan_destroy(h)
+        self._drop_fourier_plan()
+
+    def _drop_fourier_plan(self):
+        fp, self._fplan = getattr(self, '_fplan', None), None
+        if fp is not None:
+            fp.close()
 
     def _join(self):
         """A plan solve returns with S completing in stream order on ITS stream.  Everything that reads or overwrites S
@@ -125,6 +132,7 @@ class ResidentProblem:
         st = _lib.stream_arg(self.dev)
         for h in self._plans.values():
             _lib.check(self.L.xinv_plan_refresh(h, st))
+        self._drop_fourier_plan()                            # (its factors are the old A and C: remade on the next solve_fourier)
 
     def _plan(self, opt, st):
         key = tuple(sorted(opt.items()))
@@ -187,6 +195,63 @@ class ResidentProblem:
         _lib.check(rc)
         self.flags[:] = fl[-1]
         return fl, _lib.last_stats()
+
+    # ---- the direct Fourier solve on the resident batch (xinvert_amd/fourier.py: FourierPlan) ------------------------
+    def _fourier_plan(self):
+        """The batch's FourierPlan, made on first use: the eligibility test of the front end on the resident data (B zero,
+        BCs, A and C one value per row or constant along x -- one comparison on the device --, the row length), then the
+        factors.  `refresh()` drops it."""
+        from . import fourier
+        import torch
+        if self._fplan is not None:
+            return self._fplan
+        if self.kind != 'std2d':
+            fourier.resident_eligible(self.kind, False, None, None, (), 0, 0)
+        yc, xc = self.core
+        B = self.coefs[1]
+        rows, varies = {}, []
+        for name, k in (('A', 0), ('C', 2)):
+            c = self.coefs[k]
+            if not (self.rowconst >> k) & 1:
+                first = c[..., :1]
+                if not bool(((c == first) | (torch.isnan(c) & torch.isnan(first))).all()):
+                    varies.append(name)
+                c = c[..., 0].contiguous()
+            rows[name] = c
+        fourier.resident_eligible(self.kind, B is not None and bool((B != 0).any()), self.p['BCy'], self.p['BCx'], varies, yc, xc)
+        self._fplan = fourier.FourierPlan(rows['A'], rows['C'], self.nb, yc, xc, self.p['delxSqr'], self.p['ratioSqr'],
+                                          undef=self.p['undef'], device=self.device)
+        return self._fplan
+
+    def solve_fourier(self, stream=None, wait=True):
+        """The direct Fourier solve of the resident batch (2-D standard form, B zero, BCs fixed / periodic, A and C constant
+        along x: DESIGN.md 4.16) on a plan that is made on first use and kept: S rows 1 .. yc-2 are overwritten with the
+        solution of the forcing `coefs[-1]` as it stands now (writing a new forcing into it needs no `refresh()`).
+        wait=True -> flags [nb, 3] = [overflow, 0, 0]; wait=False queues only and returns None: `fourier_status()` has the
+        flags.  A member that holds `undef` where the solve reads keeps its S; the status raises XinvError naming it."""
+        import torch
+        with torch.cuda.device(self.dev):
+            plan = self._fourier_plan()
+        cur = torch.cuda.current_stream(self.dev)
+        st = stream if stream is not None else cur
+        if st.cuda_stream != cur.cuda_stream:
+            self._join()
+            st.wait_stream(cur)
+            self._last_stream = st
+        else:
+            self._join()
+        plan.solve(self.S, self.coefs[-1], stream=st)
+        return self.fourier_status() if wait else None
+
+    def fourier_status(self):
+        """Wait for the last `solve_fourier` -> flags [nb, 3] (also `self.flags`)."""
+        if self._fplan is None:
+            raise _lib.XinvError('fourier_status: no solve_fourier has been queued')
+        try:
+            self._fplan.status()
+        finally:
+            self.flags[:] = self._fplan.flags
+        return self.flags
 
     def full_arrays(self):
         """The coefficient stack as the entries that take full arrays want it -> (arrays, strides of S and the arrays):
