@@ -319,7 +319,10 @@ def deriv(v, dim, BCs=('extend', 'extend'), fill=(0, 0), scale=1, scheme='center
 
 def deriv2(v, dim, BCs=('extend', 'extend'), fill=(0, 0), scale=1, dims=None):
     """Second derivative along `dim` (reference finitediffs.py:662-702), one kernel launch: the second difference of
-    the BC-padded field over the squared lower spacing of the padded coordinate, then over scale ** 2."""
+    the BC-padded field over the squared lower spacing of the padded coordinate, then over scale ** 2.
+
+    That is the reference's formula, and it is a second derivative only where the spacing is uniform: on a stretched
+    coordinate (pressure levels) the result does not converge to f'' however fine the grid."""
     f = _field(v, dims)
     call = _Call(f, _EACH)
     call.term(f, dim, 'second', BCs, fill, scale)
@@ -513,7 +516,8 @@ class FiniteDiff:
 
     def Laplacian(self, v, dims=['X', 'Y'], BCs=None, fill=None):
         """Laplacian of a scalar (one launch): the second derivatives along `dims` summed in their order, with the
-        lat-lon metric term on Y and the points at |lat| == 90 set to 0."""
+        lat-lon metric term on Y and the points at |lat| == 90 set to 0.  Each second derivative is `deriv2`'s: along a
+        non-uniform dim (pressure levels as 'Z') it is not consistent."""
         BCs = _overwriteBCs(BCs, self.BCs)
         fill = _overwriteFills(fill, self.fill)
         llc = self.coords == 'lat-lon'
