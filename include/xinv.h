@@ -512,6 +512,18 @@ int xinv_standard_1d_f64_dev(double *S, const double *A, const double *B, const 
  *   xinv_fourier_plan_solve_f64_dev(plan, S, F, sS, sF, stream)
  *   xinv_fourier_plan_status(plan, flags, bad)
  *   xinv_fourier_plan_destroy(plan)
+ * The general form -- A Syy + C Sxx + D Sy + E Sx + F S = G with B == 0, A, C, D, E, F functions of y alone, BCy fixed,
+ * BCx periodic, no mask (Gill-Matsuno, Stommel on a periodic channel) -- decouples the same way, into one COMPLEX
+ * tridiagonal system per wavenumber: lo_j = A[j] ratioSqr - D[j] ratio delx / 2, up_j = A[j] ratioSqr + D[j] ratio delx / 2,
+ * Re di_jk = -(2 A[j] ratioSqr + C[j] lambda_k) + F[j] delxSqr, Im di_jk = E[j] delx sin(2 pi k / xc); every coefficient
+ * is read at row j only.  It is the fixed point of xinv_general_2d_f64's sweeps, reached without one -- also where the
+ * sweeps diverge: diagonal dominance is not required, the march does not pivot, the overflow word and the residual
+ * (xinv_residual_general_2d_f64_dev) are the safety net.  delx, delxSqr, ratio and ratioSqr are taken as given, as the
+ * sweeps take them.  The contract is the standard-form pair's: one value per row for A, C, D, E, F; strides[7] of S, A, C,
+ * D, E, F, G; flags[m] = {overflow, 0, 0}; `undef` on rows 1 .. yc-2 of G, A, C, D, E, F or on rows 0, yc-1 of S in any
+ * member -> XINV_ERR_ARG naming the member, every S untouched; the same row lengths; the same workspace discipline.
+ *   xinv_fourier_general_2d_f64_dev(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef, flags, stream)
+ *   xinv_fourier_general_2d_f64_batched(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef, flags, opt)
  * The prototypes live in a header of their own, which this one includes: a caller of xinv.h has them. */
 #include "xinv_fourier.h"
 

@@ -23,6 +23,21 @@ int xinv_fourier_standard_2d_f64_batched(double *S, const double *A, const doubl
                                          const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr,
                                          double undef, double *flags, const xinv_options *opt);
 
+/* The 2-D GENERAL form, B == 0 (xinv.h, "fourier": the general form): one complex tridiagonal system per wavenumber
+ * (k_fourier_gcheck, k_fourier_cfactor, k_fourier_csubst of csrc/xinv_cfourier.h around k_rowdft).  A, C, D, E, F: one
+ * value per row; strides[7]: of S, A, C, D, E, F, G between two members, 0 = shared (not S), else >= yc (S, G: yc * xc).
+ * The contract of the standard-form pair: flags = [overflow, 0, 0] per member, rows 0 and yc-1 of S are not written, a
+ * member that holds `undef` at a point that is read makes the call return XINV_ERR_ARG with every S untouched. */
+int xinv_fourier_general_2d_f64_dev(double *S, const double *A, const double *C, const double *D, const double *E,
+                                    const double *F, const double *G, int64_t nbatch, const int64_t *strides, int64_t yc,
+                                    int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr, double undef,
+                                    double *flags, void *stream);
+
+int xinv_fourier_general_2d_f64_batched(double *S, const double *A, const double *C, const double *D, const double *E,
+                                        const double *F, const double *G, int64_t nbatch, const int64_t *strides,
+                                        int64_t yc, int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr,
+                                        double undef, double *flags, const xinv_options *opt);
+
 /* device pointers; the transform is queued on `stream` */
 int xinv_rowdft_f64_dev(double *out, const double *in, int64_t nrows, int64_t n, int inverse, void *stream);
 

@@ -12,8 +12,8 @@ Layout (only what the hot path needs):
   finitediffs.py FiniteDiff / deriv / deriv2 / padBCs: one HIP launch per operator (reference xinvert/finitediffs.py)
   utils.py       loop_noncore (reference xinvert/utils.py)
   tridiag.py     trace / traceCyclic: batched tridiagonal direct solves, one system per lane (reference xinvert/numbas.py)
-  fourier.py     rfft_rows / irfft_rows, the eligibility test of iParams['method'] = 'fourier' (the direct 2-D solve), and
-                 FourierPlan: the factors of one operator kept across solves
+  fourier.py     rfft_rows / irfft_rows, the eligibility tests of iParams['method'] = 'fourier' / 'cfourier' (the direct 2-D
+                 solves of the standard and the general form), and FourierPlan: the factors of one operator kept across solves
   multigrid.py   invert_MultiGrid: coarse-to-fine SOR solves, HIP restriction / prolongation (reference xinvert/apps.py)
 """
 from .field import Field                                           # noqa: F401

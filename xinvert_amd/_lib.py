@@ -83,6 +83,7 @@ EXPORTS = [
     'xinv_fourier_standard_2d_f64_dev', 'xinv_fourier_standard_2d_f64_batched', 'xinv_rowdft_f64_dev',
     'xinv_fourier_plan_create_standard_2d_f64_dev', 'xinv_fourier_plan_solve_f64_dev', 'xinv_fourier_plan_status',
     'xinv_fourier_plan_destroy',
+    'xinv_fourier_general_2d_f64_dev', 'xinv_fourier_general_2d_f64_batched',
     'xinv_plan_create_standard_2d_f64_dev', 'xinv_plan_create_general_2d_f64_dev',
     'xinv_plan_create_standard_3d_f64_dev', 'xinv_plan_create_general_3d_f64_dev',
     'xinv_plan_create_general_bih_2d_f64_dev', 'xinv_plan_create_standard_2d_test_f64_dev',
@@ -140,6 +141,11 @@ def load():
     L.xinv_fourier_standard_2d_f64_dev.argtypes = [_vp] * 4 + four_tail + [_vp]
     L.xinv_fourier_standard_2d_f64_batched.argtypes = [_dp] * 4 + four_tail + [_opt]
     L.xinv_rowdft_f64_dev.argtypes = [_vp, _vp, _i64, _i64, _int, _vp]
+    # ... of the general form: S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef, flags
+    # (host), stream / opt
+    cfour_tail = [_i64, _ip, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _dp]
+    L.xinv_fourier_general_2d_f64_dev.argtypes = [_vp] * 7 + cfour_tail + [_vp]
+    L.xinv_fourier_general_2d_f64_batched.argtypes = [_dp] * 7 + cfour_tail + [_opt]
     # its plans: create(&plan, A, C, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef, stream); solve(plan, S, F, sS, sF,
     # stream); status(plan, flags (host), bad (host int32 or NULL)); destroy(plan)
     L.xinv_fourier_plan_create_standard_2d_f64_dev.argtypes = [_pvp, _vp, _vp, _i64, _ip, _i64, _i64, _f64, _f64, _f64, _vp]

@@ -539,12 +539,12 @@ def _template(coef_func, inv_func, dimLen, F, dims, coords='lat-lon', icbc=None,
     # 1. coefficients (`_lazy`: builders that can may describe the forcing instead of computing it;
     #    iParams['device_prep'] = False keeps everything on the host, as the reference)
     #    iParams['residual'] = True: the residual is evaluated on the solver state below, which a lazy forcing never
-    #    brings to the host -- so the forcing is built here; iParams['method'] = 'fourier' takes host arrays too
+    #    brings to the host -- so the forcing is built here; iParams['method'] = 'fourier' / 'cfourier' take host arrays too
     want_resid = bool(iParams.get('residual')) and _res_func(inv_func) is not None
     if iParams.get('residual') and not want_resid:
         raise Exception("iParams['residual'] is available for the second-order 2-D and 3-D forms only, not for "
                         + inv_func.__name__)
-    iParams['_lazy'] = not want_resid and iParams.get('method', 'sor') != 'fourier'
+    iParams['_lazy'] = not want_resid and iParams.get('method', 'sor') not in ('fourier', 'cfourier')
     maskF, initS, coeffs = coef_func(F, dims, coords, mParams, iParams, icbc)
     iParams.pop('_lazy', None)
 

@@ -62,6 +62,8 @@ UNITS = [
     ('xinv_tu_resid', 'xinv_tu_resid.hip', []),
     # the direct Fourier solve of the 2-D standard form for periodic x (k_rowdft, k_fourier_tri, k_fourier_check)
     ('xinv_tu_fourier', 'xinv_tu_fourier.hip', []),
+    # ... and of the 2-D general form (k_fourier_cfactor, k_fourier_csubst, k_fourier_gcheck): a unit of its own
+    ('xinv_tu_cfourier', 'xinv_tu_cfourier.hip', []),
 ]
 # XINV_VARIANT_UNITS="xinv_tu_fused3d,..." (with XINV_BUILD_TAG): only these units are compiled with the extra flags; every
 # other object is taken from the shipped build's build/obj (a variant of one kernel family links in seconds)

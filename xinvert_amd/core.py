@@ -48,7 +48,8 @@ def inv_standard2D_test(A, B, C, D, E, F, S, dims, iParams):
 
 
 def inv_general2D(A, B, C, D, E, F, G, S, dims, iParams):
-    """A Syy + B Syx + C Sxx + D Sy + E Sx + F S = G   (reference core.py:374-444)."""
+    """A Syy + B Syx + C Sxx + D Sy + E Sx + F S = G   (reference core.py:374-444).  iParams['method'] = 'cfourier': B == 0,
+    A, C, D, E, F functions of y alone, BCs ['fixed', 'periodic'], no mask -- solved directly (xinvert_amd/fourier.py)."""
     if len(dims) != 2:
         raise Exception('2 dimensions are needed for inversion')
     return _solve('gen2d', (A, B, C, D, E, F), G, S, dims, iParams)
@@ -174,10 +175,15 @@ def _prep_coef(c, F, perm, core_shape, nbatch, allow_null=False):
 
 def _method(kind, iParams):
     """iParams['method']: 'sor' (default); 'direct', which only the 1-D standard form has; 'fourier', which only the 2-D
-    standard form has (xinvert_amd/fourier.py: periodic x, coefficients constant along x, no mask)."""
+    standard form has (xinvert_amd/fourier.py: periodic x, coefficients constant along x, no mask); 'cfourier', the same
+    for the 2-D general form with B == 0 (one complex system per wavenumber)."""
     method = iParams.get('method', 'sor')
-    if method not in ('sor', 'direct', 'fourier'):
-        raise Exception("iParams['method'] must be 'sor' or 'direct' (or 'fourier', for inv_standard2D), got %r" % (method,))
+    if method not in ('sor', 'direct', 'fourier', 'cfourier'):
+        raise Exception("iParams['method'] must be 'sor' or 'direct' (or 'fourier', for inv_standard2D; or 'cfourier', for "
+                        "inv_general2D), got %r" % (method,))
+    if method == 'cfourier' and kind != 'gen2d':
+        raise Exception("iParams['method'] = 'cfourier' is available for the 2-D general form only (inv_general2D and the "
+                        "apps on it), not for %s; 'sor' solves this case" % forms.FORMS[kind].inv)
     if method == 'direct' and kind != 'std1d':
         raise Exception("iParams['method'] = 'direct' is available for the 1-D standard form only (inv_standard1D, "
                         "invert_GeoAdjustment, invert_RefStateSWM), not for %s" % forms.FORMS[kind].inv)
@@ -464,10 +470,57 @@ def _solve_fourier(coefs, F, S, dims, iParams):
     return S
 
 
+def _solve_cfourier(coefs, G, S, dims, iParams):
+    """iParams['method'] = 'cfourier': one call of xinv_fourier_general_2d_f64_batched on every slice (float64; the forcing
+    built on the host; A, C, D, E and F travel as one value per row).  optArg, mxLoop and tolerance play no part; flags =
+    [overflow, 0, 0].  A call outside the path's scope raises before anything runs (fourier.eligible_general)."""
+    from . import fourier
+    if not isinstance(G, Field) or not (isinstance(S, Field) or S is None):
+        raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
+    devs = iParams.get('devices')
+    if devs is not None and (isinstance(devs, str) or len(list(devs)) > 1):
+        raise NotImplementedError("iParams['method'] = 'cfourier' runs on one device: name it with iParams['device']")
+    perm, bdims, bshape = _batch_layout(G, dims)
+    core_shape = tuple(G.shape[G.axis(d)] for d in dims)
+    nbatch = int(np.prod(bshape)) if bshape else 1
+    yc, xc = core_shape
+    n = yc * xc
+    if nbatch == 0:
+        return S if S is not None else G.like(np.zeros(G.shape))
+    if S is None:
+        S = G.like(np.zeros(G.shape))
+    tr = lambda v: np.ascontiguousarray(np.transpose(np.asarray(v, dtype=np.float64), perm)).reshape((nbatch,) + core_shape)
+    Gv, Sv = tr(G.values), tr(S.values)
+    cs = [_prep_coef(c, G, perm, core_shape, nbatch, allow_null=(k == 1)) for k, c in enumerate(coefs)]
+    rows = fourier.eligible_general(*[(c[0], c[2]) for c in cs], Gv, Sv, iParams['BCs'], _undeftmp)
+    L = _lib.require_gpu()
+    strides = [n] + [yc if r.ndim == 2 else 0 for r in rows] + [n]
+    flags = np.zeros((nbatch, 3))
+    rc = L.xinv_fourier_general_2d_f64_batched(_lib.hptr(Sv), *[_lib.hptr(r) for r in rows], _lib.hptr(Gv), nbatch,
+                                               _lib.strides_arg(strides), yc, xc, float(iParams['del1']),
+                                               float(iParams['del1Sqr']), float(iParams['ratio']), float(iParams['ratioSqr']),
+                                               _undeftmp, _lib.hptr(flags), _lib.options(device=int(iParams.get('device', -1))))
+    _lib.check(rc)
+    out = np.transpose(Sv.reshape(tuple(bshape) + core_shape), np.argsort(perm))
+    if S.values.dtype == out.dtype and S.values.flags.writeable:
+        S.values[...] = out
+    else:
+        S.values = np.ascontiguousarray(out)
+    iParams['flags'] = flags if nbatch > 1 else flags[0]
+    iParams['stats'] = _lib.last_stats()
+    if iParams.get('printInfo', True):
+        coords = [np.asarray(G[d]) for d in bdims]
+        for m, idx in enumerate(itertools.product(*coords) if bdims else [()]):
+            print(_info(dict(zip(bdims, idx))) + ' fourier solve' + (' (overflows!)' if flags[m, 0] else ''))
+    return S
+
+
 def _solve(kind, coefs, F, S, dims, iParams):
     method = _method(kind, iParams)
     if method == 'fourier':
         return _solve_fourier(coefs, F, S, dims, iParams)
+    if method == 'cfourier':
+        return _solve_cfourier(coefs, F, S, dims, iParams)
     direct = method == 'direct'
     if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
         raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')

@@ -46,15 +46,16 @@ static int fourier_factor(int64_t n, int *radix, int *npass)
     return XINV_OK;
 }
 
-// The tables of one row length: [n] complex exp(-2 pi i t / n), then [K] lambda_k = 4 sin^2(pi k / n), rounded once from
-// long double.  Built on the first call with that length and kept for the life of the process (at most 96 KB each), so a
-// queued kernel never sees its table change.  Under the workspace's lock.
+// The tables of one row length: [n] complex exp(-2 pi i t / n), then [K] lambda_k = 4 sin^2(pi k / n), then [K] sigma_k =
+// sin(2 pi k / n) (the general form's: xinv_cfourier.h; sigma_0 and, for even n, sigma_{n/2} are exactly 0), rounded once
+// from long double.  Built on the first call with that length and kept for the life of the process (at most 128 KB each),
+// so a queued kernel never sees its table change.  Under the workspace's lock.
 static int fourier_tables(Workspace *ws, int64_t n, const double **tab)
 {
     for (const auto &e : ws->four_tab)
         if (e.first == n) { *tab = e.second; return XINV_OK; }
     const int64_t K = n / 2 + 1;
-    std::vector<double> h((size_t)(2 * n + K));
+    std::vector<double> h((size_t)(2 * n + 2 * K));
     const long double pi = 3.14159265358979323846264338327950288L;
     for (int64_t t = 0; t < n; t++) {
         const long double ang = 2.0L * pi * (long double)t / (long double)n;
@@ -64,6 +65,7 @@ static int fourier_tables(Workspace *ws, int64_t n, const double **tab)
     for (int64_t k = 0; k < K; k++) {
         const long double s = sinl(pi * (long double)k / (long double)n);
         h[2 * n + k] = (double)(4.0L * s * s);
+        h[2 * n + K + k] = (k == 0 || 2 * k == n) ? 0.0 : (double)sinl(2.0L * pi * (long double)k / (long double)n);
     }
     double *d = nullptr;
     HIPCHK(hipMalloc((void **)&d, h.size() * sizeof(double)));

@@ -75,6 +75,7 @@ static inline void xinv_cpu_relax()
 #include "xinv_mg.h"           /* multigrid grid transfers (k_mg_restrict, k_mg_prolong) */
 #include "xinv_resid_host.h"   /* the residual L(S) - F of the second-order forms (k_resid2d, k_resid3d) */
 #include "xinv_fourier_host.h" /* the direct Fourier solve of the 2-D standard form for periodic x (k_rowdft, k_fourier_tri) */
+#include "xinv_cfourier_host.h" /* ... and of the 2-D general form (k_fourier_cfactor, k_fourier_csubst) */
 
 // ------------------------------------------------------------------ C-ABI
 extern "C" {
@@ -542,6 +543,39 @@ int xinv_fourier_standard_2d_f64_batched(double *S, const double *A, const doubl
                                          double undef, double *flags, const xinv_options *opt)
 {
     GUARD(fourier_host(mk_fourier(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags, opt))
+}
+
+// ... of the 2-D general form (cfourier_* of xinv_cfourier_host.h)
+static CFourierCall mk_cfourier(double *S, const double *A, const double *C, const double *D, const double *E, const double *F,
+                                const double *G, int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc, double delx,
+                                double delxSqr, double ratio, double ratioSqr, double undef)
+{
+    CFourierCall c;
+    memset(&c, 0, sizeof c);
+    c.S = S; c.c[0] = A; c.c[1] = C; c.c[2] = D; c.c[3] = E; c.c[4] = F; c.G = G;
+    c.nbatch = nbatch; c.yc = yc; c.xc = xc;
+    if (strides)
+        for (int q = 0; q < 7; q++) c.s[q] = strides[q];
+    c.delx = delx; c.delxSqr = delxSqr; c.ratio = ratio; c.ratioSqr = ratioSqr; c.undef = undef;
+    return c;
+}
+
+int xinv_fourier_general_2d_f64_dev(double *S, const double *A, const double *C, const double *D, const double *E,
+                                    const double *F, const double *G, int64_t nbatch, const int64_t *strides, int64_t yc,
+                                    int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr, double undef,
+                                    double *flags, void *stream)
+{
+    GUARD(cfourier_dev(mk_cfourier(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
+                       flags, (hipStream_t)stream))
+}
+
+int xinv_fourier_general_2d_f64_batched(double *S, const double *A, const double *C, const double *D, const double *E,
+                                        const double *F, const double *G, int64_t nbatch, const int64_t *strides,
+                                        int64_t yc, int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr,
+                                        double undef, double *flags, const xinv_options *opt)
+{
+    GUARD(cfourier_host(mk_cfourier(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
+                        flags, opt))
 }
 
 int xinv_rowdft_f64_dev(double *out, const double *in, int64_t nrows, int64_t n, int inverse, void *stream)

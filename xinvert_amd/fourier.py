@@ -1,6 +1,7 @@
 """The direct Fourier solve of the 2-D standard form for periodic x (iParams['method'] = 'fourier'; include/xinv.h,
 "fourier"): the row transform for callers who want the spectrum, the eligibility test of the front end, and FourierPlan
-for callers who solve one operator again and again (the factors are kept; a solve only queues).
+for callers who solve one operator again and again (the factors are kept; a solve only queues).  eligible_general is the
+eligibility test of iParams['method'] = 'cfourier', the same solve for the 2-D general form (B == 0, complex systems).
 
 rfft_rows / irfft_rows are numpy.fft.rfft / irfft along the last axis of a CUDA float64 tensor, on the HIP kernel k_rowdft
 (queued on the current stream).  Row lengths are products of 2, 3 and 5 up to MAX_N.  There is no CPU fallback.
@@ -171,8 +172,8 @@ class FourierPlan:
         return self.flags, self.bad
 
 
-def _refuse(why):
-    raise Exception("iParams['method'] = 'fourier': %s; 'sor' solves this case" % why)
+def _refuse(why, method='fourier'):
+    raise Exception("iParams['method'] = '%s': %s; 'sor' solves this case" % (method, why))
 
 
 def resident_eligible(kind, B_nonzero, BCy, BCx, varies, yc, xc):
@@ -197,15 +198,43 @@ def resident_eligible(kind, B_nonzero, BCy, BCx, varies, yc, xc):
         _refuse(err)
 
 
-def _per_row(name, a, rowconst):
+def _per_row(name, a, rowconst, method='fourier'):
     """A coefficient as _prep_coef hands it over -> one float64 value per row ([yc] or [nbatch, yc])."""
     a = np.asarray(a, dtype=np.float64)
     if rowconst:                                         # (a stride-0 view along x: only its first column travelled)
         return np.ascontiguousarray(a)
     first = a[..., :1]
     if not ((a == first) | (np.isnan(a) & np.isnan(first))).all():     # (a NaN row -- cos beyond the pole -- is constant too)
-        _refuse('%s must be constant along x (the array %s varies along it)' % (name, name))
+        _refuse('%s must be constant along x (the array %s varies along it)' % (name, name), method)
     return np.ascontiguousarray(a[..., 0])
+
+
+def eligible_general(A, B, C, D, E, Fc, Gv, Sv, BCs, undef):
+    """The conditions of the Fourier path of the 2-D general form ('cfourier') on the host arrays of one call, in the order
+    of DESIGN.md 4.16, "General form"; the first that fails raises an Exception naming it.  A .. Fc: (array, rowconst) as
+    core._prep_coef returns them (B: None = identically zero); Gv, Sv [nbatch, yc, xc].  -> [A, C, D, E, Fc] as one value
+    per row.  Diagonal dominance is NOT a condition: the overflow flag and the residual are the safety net."""
+    no = lambda why: _refuse(why, 'cfourier')
+    if B[0] is not None and np.any(np.asarray(B[0]) != 0):
+        no('B must be identically zero (the array B is not)')
+    BCs = list(BCs)
+    if BCs[0] != 'fixed':
+        no("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCs[0],))
+    if BCs[1] != 'periodic':
+        no("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCs[1],))
+    rows = [_per_row(name, *c, method='cfourier') for name, c in zip('ACDEF', (A, C, D, E, Fc))]
+    pts = [('G', Gv[:, 1:-1], '1 .. yc-2')] + [(name, r[..., 1:-1], '1 .. yc-2') for name, r in zip('ACDEF', rows)] + \
+          [('S', Sv[:, [0, -1]], '0 and yc-1')]
+    for name, p, where in pts:
+        if (p == undef).any():
+            no('no undefined value may sit at a point the solve reads (the array %s holds one on rows %s)' % (name, where))
+    yc, xc = Gv.shape[-2:]
+    if yc < 3:
+        no('yc must be at least 3, got %d' % yc)
+    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
+    if err:
+        no(err)
+    return rows
 
 
 def eligible(A, B, C, Fv, Sv, BCs, undef):
