@@ -36,7 +36,7 @@ struct Plan {
     double lone = 1.6;       // planner: cost of a workgroup alone on its CU relative to one of a pair
     bool pipe;               // K == 4 passes run the wave-pipelined kernel (k_pipe2d): one tile per workgroup
     int tpw;                 // wave-tiles per workgroup of the planned kernel: 4, or 1 with `pipe`
-    bool pipe_fr;            // `pipe`: the forcing rides the LDS ring (launches whose arrays exceed the caches)
+    bool pipe_fr;            // `pipe`: the forcing rides the LDS ring (xinv_tiles.h: xinv_pipe_forcing_ring)
     int64_t xc;              // the problem's row length (the ring layout's strip width depends on it: xinv_tiles.h)
     bool fma;                // XINV_FLAG_FMA: the contracted-arithmetic kernel variants (per-row-coefficient forms only)
     bool alias_ac;           // `pq`: A and C hold the same numbers everywhere -- C is read out of A (FusedGen2DQA, kernel mask um | 2)

@@ -328,10 +328,10 @@ static int plan5_sweeps(const Problem &p, const xinv_options &opt, Workspace *, 
     }
     pl.pipe = pipe_want && pl.K == XINV_PIPE_P;
     pl.tpw = pl.pipe ? 1 : 4;
-    // the forcing through the LDS ring where the launch's streams (S read + write + forcing, every member) no
-    // longer fit the caches and the later wavefronts' forcing requests would go back to HBM; XINV_PIPE_FR=0|1 forces
+    // the forcing through the LDS ring from the size on at which the later wavefronts' forcing requests cost more than
+    // the ring does (xinv_tiles.h: xinv_pipe_forcing_ring; the headline's 155 MB is above it); XINV_PIPE_FR=0|1 forces
     const int fr_env = opt.pipe_fr ? (opt.pipe_fr > 0 ? 1 : 0) : XINV_ENV_INT("XINV_PIPE_FR", -1);
-    const bool fr_size = (double)p.nbatch * (double)p.yc * (double)p.xc * 24.0 > 2.0e8;
+    const bool fr_size = xinv_pipe_forcing_ring(p.nbatch, p.yc, p.xc);
     pl.pipe_fr = pl.pipe && (fr_env < 0 ? fr_size : fr_env != 0);
     return XINV_OK;
 }

@@ -245,6 +245,21 @@ __host__ __device__ inline int64_t xinv_pipe_mask_index(int64_t m, int nstrip, i
 // ---- the planner's cost models (host only; pure integer / double arithmetic, checked on the CPU) --------------------------
 __host__ inline int64_t xinv_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// k_pipe2d: does the forcing row ride the LDS ring behind S (FR: wavefront 0 reads it once, wavefronts 1..3 take it out
+// of LDS), or does every wavefront ask the memory system for it?  Decided by the bytes the launch streams -- S read, S
+// written and the forcing, 24 B per point of every member.  Beyond the caches the later wavefronts' requests go back to
+// HBM, and FR wins by 10-20 % (profiles/r03_pipe_size_crossover.txt: the round-3 switch, 200 MB).  But their requests
+// cost time when they HIT as well: with them compiled out the headline launch is 2.7 us shorter, and FR, which trades the
+// three buffer loads of a workgroup's step for three LDS writes and reads, takes 0.4-1.0 us of that back at 155 MB, 3-5 %
+// of the launch at 100-200 MB (four and eight Gill-Matsuno members); at 39 MB and below, where the tiles are short and
+// few workgroups share a CU, the larger ring loses 0-2.5 % (profiles/pipe2d_norm_wave.txt).  The switch sits between
+// the two measured sides.
+#define XINV_PIPE_FR_BYTES 8.0e7
+__host__ inline bool xinv_pipe_forcing_ring(int64_t nbatch, int64_t yc, int64_t xc)
+{
+    return (double)nbatch * (double)yc * (double)xc * 24.0 > XINV_PIPE_FR_BYTES;
+}
+
 // The tallest tile of the even split of yc rows into nrb blocks (xinv_tile_rows with RY == 0: boundaries at
 // floor(k yc / nrb) rounded down to even rows, the last block ends at yc), in closed form: with yc = 2 nrb q + s the
 // boundaries are 2 (k q + floor(k s / (2 nrb))); a block before the last has 2 q rows, or 2 q + 2 when the fraction
