@@ -108,6 +108,8 @@ struct FusedArgs {
     const void *rowf;          // k_pipe2d: [nbatch][yc] per-row records (M::PIPE_RW doubles each, xinv_pipe2d.h)
     const unsigned long long *pmask;   // k_pipe2d: [nbatch][nstrip][yc] update masks, two lane words each (xinv_tiles.h:
                                // xinv_pipe_mask_index; k_pipe_masks builds them once per plan)
+    const void *trec;          // k_pipe2d: [nbatch or 1][nwg] tile records (xinv_tiles.h: PipeTileRec), built with the plan;
+    int trec_ms;               // their member stride in records (0: one set for every member -- no tile list)
     double *dbg;               // test-hooks build only: the hook record {tile, launch tag, member} (xinv_hook_withhold);
                                // test-hooks build (XINV_TEST_HOOKS): three ints {tile, launch tag, member} -- that tile of
                                // that launch withholds its norm partial, so that the reducer REALLY times out
@@ -539,13 +541,6 @@ template <class M> struct ModelFma<M, std::void_t<decltype(M::FMA)>> { static co
 
 template <int NC> struct RowPack { double2 s; double2 c[NC]; double cs[NC]; };
 
-struct LaneCols {
-    int64_t l0, l1;            // load columns of .x / .y (wrapped or clamped)
-    bool ok_x, ok_y;           // column may be updated (interior, or any column when periodic)
-    bool use_x, use_y;         // column is owned (stored / counted) by this lane
-    int cls_x, cls_y;          // extend fix: 0 none, 1 straight copy, 2 column 0, 3 column xc-1
-};
-
 template <bool AL>
 __device__ __forceinline__ double2 ld2(const double *p, int64_t row_off, const LaneCols &lc)
 {
@@ -553,36 +548,7 @@ __device__ __forceinline__ double2 ld2(const double *p, int64_t row_off, const L
     double2 v; v.x = p[row_off + lc.l0]; v.y = p[row_off + lc.l1]; return v;
 }
 
-// Lane -> column map of one wavefront's strip: lane owns columns c0 = xu0 - H + 2*lane and c0+1.
-template <bool AL>
-__device__ __forceinline__ LaneCols make_lanecols(int64_t xu0, int H, int UW, int lane, int64_t xc,
-                                                  bool per)
-{
-    LaneCols lc;
-    const int64_t c0 = xu0 - H + 2 * lane, c1 = c0 + 1;
-    if (per) {
-        int64_t w0 = c0 % xc; if (w0 < 0) w0 += xc;
-        int64_t w1 = c1 % xc; if (w1 < 0) w1 += xc;
-        lc.l0 = w0; lc.l1 = w1;
-        lc.ok_x = lc.ok_y = true;
-        lc.cls_x = lc.cls_y = 1;
-    } else {
-        if (AL) {
-            int64_t p = c0 < 0 ? 0 : (c0 > xc - 2 ? xc - 2 : c0);
-            lc.l0 = p; lc.l1 = p + 1;
-        } else {
-            lc.l0 = c0 < 0 ? 0 : (c0 > xc - 1 ? xc - 1 : c0);
-            lc.l1 = c1 < 0 ? 0 : (c1 > xc - 1 ? xc - 1 : c1);
-        }
-        lc.ok_x = (c0 >= 1 && c0 <= xc - 2);
-        lc.ok_y = (c1 >= 1 && c1 <= xc - 2);
-        lc.cls_x = lc.ok_x ? 1 : (c0 == 0 ? 2 : (c0 == xc - 1 ? 3 : 0));
-        lc.cls_y = lc.ok_y ? 1 : (c1 == xc - 1 ? 3 : 0);
-    }
-    lc.use_x = (c0 >= xu0 && c0 < xu0 + UW && c0 < xc);
-    lc.use_y = (c1 >= xu0 && c1 < xu0 + UW && c1 < xc);
-    return lc;
-}
+// (LaneCols, make_lanecols: the lane -> column map of one wavefront's strip, xinv_tiles.h -- shared with the host)
 
 // RING (periodic x with ODD xc; round 5, k_pipe3d): the row as an EVEN ring of xc + 1 virtual columns -- the xc real ones
 // and a phantom column P between xc-1 and 0.  Strips start on even virtual columns, so a lane's .x slot always holds an
@@ -602,16 +568,9 @@ __device__ __forceinline__ LaneCols make_lanecols(int64_t xu0, int H, int UW, in
 struct RingSeam { unsigned long long lanes; bool any; };     // lanes whose .x slot holds column xc-1 (wave-uniform mask)
 __device__ __forceinline__ LaneCols make_lanecols_ring(int64_t xu0, int HW, int UW, int lane, int64_t xc, RingSeam &rs)
 {
-    LaneCols lc;
-    const int64_t c0 = xu0 - HW + 2 * lane, c1 = c0 + 1, xv = xc + 1;
-    int64_t w0 = c0 % xv; if (w0 < 0) w0 += xv;              // (even: never P)
-    int64_t w1 = c1 % xv; if (w1 < 0) w1 += xv;
-    lc.l0 = w0; lc.l1 = (w1 == xc) ? xc - 1 : w1;
-    lc.ok_x = true; lc.ok_y = (w1 != xc);
-    lc.cls_x = lc.cls_y = 1;
-    lc.use_x = (c0 >= xu0 && c0 < xu0 + UW && c0 < xc);
-    lc.use_y = (c1 >= xu0 && c1 < xu0 + UW && c1 < xc);
-    rs.lanes = __builtin_amdgcn_ballot_w64(w0 == xc - 1);
+    bool seam_lane;
+    const LaneCols lc = xinv_lanecols_ring(xu0, HW, UW, lane, xc, seam_lane);      // (xinv_tiles.h: shared with the host)
+    rs.lanes = __builtin_amdgcn_ballot_w64(seam_lane);
     rs.any = rs.lanes != 0ull;
     return lc;
 }

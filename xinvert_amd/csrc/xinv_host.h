@@ -323,11 +323,16 @@ struct Workspace {
     // masked-tile skipping
     unsigned char *d_act = nullptr; size_t d_act_cap = 0;
     unsigned char *h_act = nullptr; size_t h_act_cap = 0;      // pinned
-    int *d_list = nullptr; size_t d_list_cap = 0;               // [nbatch][ntl] then [nbatch][nskip]
+    int *d_list = nullptr; size_t d_list_cap = 0;               // [nbatch][ntl] then [nbatch][nskip] (then k_pipe2d's tile records)
     int *h_list = nullptr; size_t h_list_cap = 0;               // pinned
+    // k_pipe2d's tile records (xinv_tiles.h: PipeTileRec) live in d_list as well: behind the lists (one upload for both), or
+    // alone when no tile is skipped -- the tiling those were built for, so that a solve without a plan that finds them in
+    // place uploads nothing (valid = 0: d_list holds something else)
+    struct TrecKey { int64_t yc, xc; int nstrip, nrb, RY, per, seam, valid; } trec_key = {0, 0, 0, 0, 0, 0, 0, 0};
     bool act_ready = false; int act_uw = 0; const double *act_f = nullptr;   // activity map issued ahead (issue_strip_active)
     bool act_synced = false;                                    // ... and its copy to the host is known to have completed
     std::vector<int> h_pre;                                     // plan_tile_skip: prefix counts (kept: no allocation per solve)
+    std::vector<PipeTileRec> h_trec;                            // plan_tile_skip: k_pipe2d's tile records by tile id (kept likewise)
     double *d_tsum = nullptr; size_t d_tsum_cap = 0;            // tsum | tcnt | xsum | xcnt
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;              // k_pipe2d: per-row records [nbatch][yc][PIPE_RW]
     unsigned long long *d_pmask = nullptr; size_t d_pmask_cap = 0;   // k_pipe2d: update masks [nbatch][nstrip][yc][2] (k_pipe_masks)

@@ -31,6 +31,8 @@ struct Plan {
     bool skip;               // masked-tile skipping: launches of K == Plan::K run the listed tiles only
     SkipNormArgs skipna;     // (the skipped tiles' geometry and list: k_skip_tiles in run_sweeps)
     int ntl, nskip;          // list entries per member (active, multiple of 4 / skipped)
+    size_t trec_off;         // `pipe`: byte offset of k_pipe2d's tile records in ws->d_list (behind the lists, 32-byte aligned)
+    int trec_ms;             // ... and their member stride in records (0: one set for every member -- no tile is skipped)
     int skip_pct;            // share of wave-tiles skipped, percent
     int skip_ppm;            // ... per million
     double lone = 1.6;       // planner: cost of a workgroup alone on its CU relative to one of a pair
@@ -231,7 +233,10 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
         a.c[sm.forcing + 1] = a.c[sm.forcing]; a.sc[sm.forcing + 1] = a.sc[sm.forcing];
         a.c[sm.forcing] = (const double *)ws->d_pfac; a.sc[sm.forcing] = p.yc * p.xc;
     }
-    if (pipe) { a.nwg = a.nstrip * a.nrb; a.rowf = ws->d_rowf; a.pmask = ws->d_pmask; }
+    if (pipe) {
+        a.nwg = a.nstrip * a.nrb; a.rowf = ws->d_rowf; a.pmask = ws->d_pmask;
+        a.trec = (const char *)ws->d_list + pl.trec_off; a.trec_ms = pl.trec_ms;    // (plan_tile_skip / plan_pipe_tile_recs)
+    }
 #if XINV_TEST_HOOKS
     a.dbg = (double *)t_hook_record;                 // (run_sweeps: XINV_HOOK_SKIP_PUBLISH; nullptr otherwise)
 #endif
@@ -598,6 +603,37 @@ static bool rows_per_tile_given(const Problem &p, const xinv_options &opt, Plan 
     return opt.rows_per_tile != 0;
 }
 
+// k_pipe2d's tile records (xinv_tiles.h: PipeTileRec): the kernel's constants they depend on
+static inline PipeTileGeom pipe_tile_geom()
+{
+    return PipeTileGeom{2 * XINV_PIPE_P, XINV_PIPE_UW, XINV_PIPE_LAG, XINV_PIPE_B, XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4};
+}
+// ... of a pipelined plan that skips no tile: one set of nstrip x nrb records for every member, alone in ws->d_list.  A
+// solve without a plan that finds the records of the same tiling in place uploads nothing (ws->trec_key).
+// (With a tile list the records ride behind it: plan_tile_skip.)
+static int plan_pipe_tile_recs(const Problem &p, Plan &pl, Workspace *ws, hipStream_t st)
+{
+    if (!pl.pipe || pl.skip) return XINV_OK;
+    const int nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    const int RY = pl.even_split ? 0 : pl.RY, nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
+    const bool per = p.BCx == XINV_BC_PERIODIC;
+    pl.trec_off = 0; pl.trec_ms = 0;
+    const Workspace::TrecKey key = {p.yc, p.xc, nstrip, nrb, RY, per ? 1 : 0, pl.seam ? 1 : 0, 1};
+    const Workspace::TrecKey &k = ws->trec_key;
+    if (ws->d_list && k.valid && k.yc == key.yc && k.xc == key.xc && k.nstrip == key.nstrip && k.nrb == key.nrb &&
+        k.RY == key.RY && k.per == key.per && k.seam == key.seam)
+        return XINV_OK;
+    const size_t bytes = (size_t)nstrip * nrb * sizeof(PipeTileRec);
+    ws->trec_key.valid = 0;
+    int rc = ensure_dev(&ws->d_list, &ws->d_list_cap, bytes);
+    if (rc) return rc;
+    if ((rc = ensure_pinned(&ws->h_list, &ws->h_list_cap, bytes, hipHostMallocDefault))) return rc;
+    xinv_pipe_identity_recs((PipeTileRec *)ws->h_list, nstrip, nrb, p.yc, RY, p.xc, per, pl.seam != 0, pipe_tile_geom());
+    HIPCHK(hipMemcpyAsync(ws->d_list, ws->h_list, bytes, hipMemcpyHostToDevice, st));
+    ws->trec_key = key;
+    return XINV_OK;
+}
+
 // Masked-tile skipping for the 5-point fused kernels.  Wave-tiles whose forcing is undefined at
 // every owned point (land, topography, polar caps) can never change (every mask predicate of the
 // reference tests the forcing), so launches run the other tiles only; the row split is re-chosen
@@ -747,9 +783,14 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
     if (nskipped == 0) return XINV_OK;
     const int nskip = (int)maxskip;
     const size_t nints = (size_t)nb * ((size_t)ntl + nskip);
-    rc = ensure_dev(&ws->d_list, &ws->d_list_cap, nints * sizeof(int));
+    // (the pipelined pass: one tile record per list entry behind the lists -- they travel in the same copy)
+    const bool recs = pl.pipe && !fixedRB;
+    const size_t rec_off = (nints * sizeof(int) + 31) & ~(size_t)31;
+    const size_t list_bytes = recs ? rec_off + (size_t)nb * ntl * sizeof(PipeTileRec) : nints * sizeof(int);
+    rc = ensure_dev(&ws->d_list, &ws->d_list_cap, list_bytes);
     if (rc) return rc;
-    if ((rc = ensure_pinned(&ws->h_list, &ws->h_list_cap, nints * sizeof(int), hipHostMallocDefault))) return rc;
+    if ((rc = ensure_pinned(&ws->h_list, &ws->h_list_cap, list_bytes, hipHostMallocDefault))) return rc;
+    ws->trec_key.valid = 0;
     int *hl = ws->h_list, *hs = ws->h_list + (size_t)nb * ntl;
     for (int64_t m = 0; m < nb; m++) {
         std::vector<int> &am = act[(size_t)m];
@@ -769,7 +810,19 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
         for (int t = 0; t < ntl; t++) hl[m * ntl + t] = t < (int)am.size() ? am[(size_t)t] : -1;
         for (int t = 0; t < nskip; t++) hs[m * nskip + t] = t < (int)skp[(size_t)m].size() ? skp[(size_t)m][t] : -1;
     }
-    HIPCHK(hipMemcpyAsync(ws->d_list, ws->h_list, nints * sizeof(int), hipMemcpyHostToDevice, st));
+    if (recs) {
+        PipeTileRec *hr = (PipeTileRec *)((char *)ws->h_list + rec_off);
+        const PipeTileGeom g = pipe_tile_geom();
+        const bool per = p.BCx == XINV_BC_PERIODIC;
+        // (a tile's record is the same for every member: built once per tile id, copied per list entry)
+        std::vector<PipeTileRec> &byid = ws->h_trec;
+        byid.resize((size_t)ntiles + 1);
+        for (int id = 0; id < (int)ntiles; id++) byid[(size_t)id] = xinv_pipe_tile_rec(id, nstrip, best, yc, 0, p.xc, per, pl.seam != 0, g);
+        byid[(size_t)ntiles] = xinv_pipe_tile_rec(-1, nstrip, best, yc, 0, p.xc, per, pl.seam != 0, g);
+        for (size_t e = 0; e < (size_t)nb * ntl; e++) hr[e] = byid[(size_t)(hl[e] < 0 ? ntiles : hl[e])];
+        pl.trec_off = rec_off; pl.trec_ms = ntl;
+    }
+    HIPCHK(hipMemcpyAsync(ws->d_list, ws->h_list, list_bytes, hipMemcpyHostToDevice, st));
     rc = ensure_dev(&ws->d_tsum, &ws->d_tsum_cap, tsum_layout(nullptr, nb, nskip).bytes);
     if (rc) return rc;
     const TsumPtrs ts = tsum_layout(ws->d_tsum, nb, nskip);

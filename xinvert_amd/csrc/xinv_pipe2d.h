@@ -606,55 +606,59 @@ __global__ __launch_bounds__(64 * XINV_PIPE_P) void k_pipe2d(FusedArgs a_)
     const FusedArgs &a = a_;
     const int64_t m = a.member0 + blockIdx.y;
     XinvCtl *ctl = a.ctl + m;
-    if (!a.force && xinv_ctl_done(ctl)) return;
-    if (a.lag && (int)blockIdx.x == a.nwg) { xinv_lag_reduce_prev(a, ctl, m); return; }
-    tag = a.lag ? a.tag : xinv_ctl_seq(ctl);
-
     const int NB = a.nwg;
     {
         const int L = blockIdx.x, q = NB >> 3, rem = NB & 7, xcd = L & 7, idx = L >> 3;
         T = xcd * q + (xcd < rem ? xcd : rem) + idx;
     }
+    // Everything the entry reads from memory goes out before the first wait: the member's stop flag and sequence number
+    // (vector loads through the coherent L2) and the tile's record (xinv_tiles.h: PipeTileRec, built with the plan; one
+    // s_load_dwordx8 through the constant address space, behind the invalidate above) are in flight together -- one
+    // round trip in every workgroup of every launch, where the list entry used to wait for the stop flag and the
+    // tile's geometry was derived behind it (a division for the strip, two 64-bit ones for the row split, two 64-bit
+    // remainders per lane for the wrapped columns).  The record of a member that turns out to be
+    // finished, or of the lag reducer's workgroup (its T is past the records: record 0), is a plain read of a valid
+    // address and is dropped.
+    typedef int xinv_v8i __attribute__((ext_vector_type(8)));
+    typedef const xinv_v8i __attribute__((address_space(4))) *xinv_ctrec_ptr;
+    const xinv_ctrec_ptr recp = (xinv_ctrec_ptr)(uintptr_t)(reinterpret_cast<const PipeTileRec *>(a.trec) +
+                                                            (m * a.trec_ms + (T < NB ? T : 0)));
+    const int done = xinv_ctl_done(ctl);
+    const unsigned seq = xinv_ctl_seq(ctl);
+    const xinv_v8i rv = *recp;
+    asm volatile("" :: "s"(rv), "s"(a.per), "s"(a.xc), "s"(a.lag), "s"(a.tag));       // (requested ahead of the early returns)
+    if (!a.force && done) return;
+    if (a.lag && (int)blockIdx.x == NB) { xinv_lag_reduce_prev(a, ctl, m); return; }
+    tag = a.lag ? a.tag : seq;
+
     // which sweep this wavefront applies: rotated from workgroup to workgroup, so that the workgroups sharing
     // a CU do not all start (and drain) their pipelines on the same SIMD
     pwi = (wave + (int)(blockIdx.x >> 8)) & (P - 1);       // (dispatch order: 8 XCDs x 32 CUs, then the next round)
-    int wt = T;
-    bool active = wt < a.nstrip * a.nrb;
-    if constexpr (SEAM) {                                // (the edge strips' tiles first: xinv_heavy_first)
-        if (!a.tile_list && NB == a.nstrip * a.nrb)
-            wt = xinv_seam_tile(xinv_heavy_first((int)blockIdx.x, NB, (a.nstrip == 1 ? 1 : 2) * a.nrb), a.nstrip, a.nrb);
-    }
-    if (a.tile_list) {
-        wt = a.tile_list[m * a.ntl + T];
-        active = wt >= 0;
-        wt = active ? wt : 0;
-    }
-    int rb = wt / a.nstrip, strip = wt - rb * a.nstrip;
-    const int64_t xc = a.xc, yc = a.yc;
-    int yu0, yu1;
-    if (a.RY > 0) {
-        yu0 = rb * a.RY;
-        yu1 = (yu0 + a.RY < (int)yc) ? yu0 + a.RY : (int)yc;
-    } else {
-        yu0 = (int)((((int64_t)rb * yc) / a.nrb) & ~(int64_t)1);
-        yu1 = (rb + 1 == a.nrb) ? (int)yc : (int)((((int64_t)(rb + 1) * yc) / a.nrb) & ~(int64_t)1);
-    }
-    // (SEAM: the ring layout's strips and halos, xinv_tiles.h)
-    const int UW = SEAM ? xinv_ring_uw(xc, H) : XINV_PIPE_UW, HW = SEAM ? xinv_ring_hw(xc, H, strip) : H;
-    const int64_t xu0 = (int64_t)strip * UW;
+    PipeTileRec rec;
+    rec.wt = rv[0]; rec.strip = rv[1]; rec.yu0 = rv[2]; rec.yu1 = rv[3]; rec.gtot = rv[4]; rec.c0 = rv[5]; rec.w0 = rv[6];
+    rec.xu0 = rv[7];
+    const bool active = rec.wt >= 0;                     // (an idle slot: the member has fewer active tiles than slots)
+    const int strip = rec.strip, yu0 = rec.yu0, yu1 = rec.yu1;
+    const int xc = (int)a.xc;
+    // (SEAM: the ring layout's strips, xinv_tiles.h)
+    const int UW = SEAM ? xinv_ring_uw(xc, H) : XINV_PIPE_UW;
     LaneCols lc[NP];
     int64_t st0[NP];
     RingSeam rs = {0ull, false};
-#pragma unroll
-    for (int q = 0; q < NP; q++) {
-        if constexpr (SEAM) lc[q] = make_lanecols_ring(xu0, HW, UW, lane, xc, rs);
-        else lc[q] = make_lanecols<AL>(xu0, H, UW, lane, xc, a.per != 0);
-        st0[q] = xu0 - HW + 2 * NP * lane + 2 * q;       // unwrapped store column of the pair's .x
+    static_assert(NP == 1, "the record's lane map: one column pair per lane");
+    {
+        if constexpr (SEAM) {
+            bool seam_lane;
+            lc[0] = xinv_lanecols_ring_rec(rec, UW, lane, xc, seam_lane);
+            rs.lanes = __builtin_amdgcn_ballot_w64(seam_lane);
+            rs.any = rs.lanes != 0ull;
+        } else lc[0] = xinv_lanecols_rec<AL>(rec, UW, lane, xc, a.per != 0);
+        st0[0] = rec.c0 + 2 * lane;                      // unwrapped store column of the pair's .x
     }
 
     if (active) {
         // global steps every wavefront goes through: the longest of the four schedules, whole barrier periods
-        const int gtot = xinv_pipe_gtot(yu1 - yu0, LAG, B, XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4);
+        const int gtot = rec.gtot;                       // (xinv_pipe_gtot of the tile's rows, out of the record)
         // SEAM: only the tiles that hold a seam lane take the march with the extra pass; every other tile of the launch
         // runs the plain one.  (One march with the extra passes behind wave-uniform branches cost EVERY tile its
         // instruction interleaving: 3601 columns ran 1.45x the time of 3600 -- profiles/r05_seam_rates.txt.)

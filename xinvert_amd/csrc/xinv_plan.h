@@ -420,8 +420,11 @@ static int plan_fused5(const Problem &p, const xinv_options &opt, Workspace *ws,
         const int rc = step(p, opt, ws, st, pl);
         if (rc) return rc;
     }
-    if (pl.even_split && !(opt.flags & XINV_FLAG_NO_TILE_SKIP)) return plan_tile_skip(p, pl, ws, st, opt);
-    return XINV_OK;
+    if (pl.even_split && !(opt.flags & XINV_FLAG_NO_TILE_SKIP)) {
+        const int rc = plan_tile_skip(p, pl, ws, st, opt);
+        if (rc) return rc;
+    }
+    return plan_pipe_tile_recs(p, pl, ws, st);           // (no tile skipped: the pipelined pass's records of the final split)
 }
 
 // which path, then the tiling of its kernel family

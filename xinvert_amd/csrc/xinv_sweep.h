@@ -735,6 +735,7 @@ struct PlanBufs {
     void *d_rowf = nullptr; size_t d_rowf_cap = 0;
     unsigned long long *d_pmask = nullptr; size_t d_pmask_cap = 0;
     int *d_list = nullptr; size_t d_list_cap = 0;
+    Workspace::TrecKey trec_key = {0, 0, 0, 0, 0, 0, 0, 0};     // (what d_list's tile records were built for travels with it)
     double *d_tsum = nullptr; size_t d_tsum_cap = 0;
     double *d_pfac = nullptr; size_t d_pfac_cap = 0;
 };
@@ -744,7 +745,7 @@ struct BufSwap {                                         // the plan's buffers s
     {
         std::swap(w->d_rowf, q->d_rowf); std::swap(w->d_rowf_cap, q->d_rowf_cap);
         std::swap(w->d_pmask, q->d_pmask); std::swap(w->d_pmask_cap, q->d_pmask_cap);
-        std::swap(w->d_list, q->d_list); std::swap(w->d_list_cap, q->d_list_cap);
+        std::swap(w->d_list, q->d_list); std::swap(w->d_list_cap, q->d_list_cap); std::swap(w->trec_key, q->trec_key);
         std::swap(w->d_tsum, q->d_tsum); std::swap(w->d_tsum_cap, q->d_tsum_cap);
         std::swap(w->d_pfac, q->d_pfac); std::swap(w->d_pfac_cap, q->d_pfac_cap);
     }

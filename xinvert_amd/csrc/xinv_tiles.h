@@ -1,7 +1,8 @@
 // xinv_tiles.h -- tile ids of the 2-D streaming kernels (k_fused2d / k_pipe2d), the dispatch order of seam launches and the
 // planner's tiling cost models:
 // integer arithmetic shared by the kernels and the planner (xinv_launch.h), and compiled on its own by the CPU suite
-// (tests/test_tiles.py builds tests/csrc/tiles_check.cpp with g++ against this header).
+// (tests/test_tiles.py builds tests/csrc/tiles_check.cpp with g++ against this header; tests/test_pipe_tile_record.py the
+// check of k_pipe2d's tile records and the lane -> column maps).
 #pragma once
 #include <cstdint>
 #ifndef __HIPCC__
@@ -240,6 +241,178 @@ __host__ __device__ inline int64_t xinv_pipe_mask_count(int64_t nbatch, int nstr
 __host__ __device__ inline int64_t xinv_pipe_mask_index(int64_t m, int nstrip, int strip, int64_t yc, int64_t row)
 {
     return ((m * nstrip + strip) * yc + row) * XINV_PIPE_MASK_WORDS;
+}
+
+// ---- lane -> column maps of the 2-D streaming kernels (k_fused2d, k_pipe2d, k_pipe_masks) ---------------------------------
+// Host-callable: the builder of k_pipe2d's tile records below is checked against them on the CPU
+// (tests/csrc/pipe_tile_record_check.cpp).
+#define XINV_HD_INLINE __host__ __device__ inline __attribute__((always_inline))
+struct LaneCols {
+    int64_t l0, l1;            // load columns of .x / .y (wrapped or clamped)
+    bool ok_x, ok_y;           // column may be updated (interior, or any column when periodic)
+    bool use_x, use_y;         // column is owned (stored / counted) by this lane
+    int cls_x, cls_y;          // extend fix: 0 none, 1 straight copy, 2 column 0, 3 column xc-1
+};
+
+// Lane -> column map of one wavefront's strip: lane owns columns c0 = xu0 - H + 2*lane and c0+1.
+template <bool AL>
+XINV_HD_INLINE LaneCols make_lanecols(int64_t xu0, int H, int UW, int lane, int64_t xc, bool per)
+{
+    LaneCols lc;
+    const int64_t c0 = xu0 - H + 2 * lane, c1 = c0 + 1;
+    if (per) {
+        int64_t w0 = c0 % xc; if (w0 < 0) w0 += xc;
+        int64_t w1 = c1 % xc; if (w1 < 0) w1 += xc;
+        lc.l0 = w0; lc.l1 = w1;
+        lc.ok_x = lc.ok_y = true;
+        lc.cls_x = lc.cls_y = 1;
+    } else {
+        if (AL) {
+            int64_t p = c0 < 0 ? 0 : (c0 > xc - 2 ? xc - 2 : c0);
+            lc.l0 = p; lc.l1 = p + 1;
+        } else {
+            lc.l0 = c0 < 0 ? 0 : (c0 > xc - 1 ? xc - 1 : c0);
+            lc.l1 = c1 < 0 ? 0 : (c1 > xc - 1 ? xc - 1 : c1);
+        }
+        lc.ok_x = (c0 >= 1 && c0 <= xc - 2);
+        lc.ok_y = (c1 >= 1 && c1 <= xc - 2);
+        lc.cls_x = lc.ok_x ? 1 : (c0 == 0 ? 2 : (c0 == xc - 1 ? 3 : 0));
+        lc.cls_y = lc.ok_y ? 1 : (c1 == xc - 1 ? 3 : 0);
+    }
+    lc.use_x = (c0 >= xu0 && c0 < xu0 + UW && c0 < xc);
+    lc.use_y = (c1 >= xu0 && c1 < xu0 + UW && c1 < xc);
+    return lc;
+}
+
+// The same for the even ring of the odd-xc periodic seam (xinv_fused.h: RING; make_lanecols_ring there adds the wave's
+// mask of seam lanes).  seam_lane: the lane's .x slot holds column xc-1.
+XINV_HD_INLINE LaneCols xinv_lanecols_ring(int64_t xu0, int HW, int UW, int lane, int64_t xc, bool &seam_lane)
+{
+    LaneCols lc;
+    const int64_t c0 = xu0 - HW + 2 * lane, c1 = c0 + 1, xv = xc + 1;
+    int64_t w0 = c0 % xv; if (w0 < 0) w0 += xv;              // (even: never P)
+    int64_t w1 = c1 % xv; if (w1 < 0) w1 += xv;
+    lc.l0 = w0; lc.l1 = (w1 == xc) ? xc - 1 : w1;
+    lc.ok_x = true; lc.ok_y = (w1 != xc);
+    lc.cls_x = lc.cls_y = 1;
+    lc.use_x = (c0 >= xu0 && c0 < xu0 + UW && c0 < xc);
+    lc.use_y = (c1 >= xu0 && c1 < xu0 + UW && c1 < xc);
+    seam_lane = (w0 == xc - 1);
+    return lc;
+}
+
+// ---- k_pipe2d: one record per tile, built with the plan ---------------------------------------------------------------------
+// Tile -> (strip, rows), the steps of its march and the origin of its lane map are functions of the plan; the kernel used
+// to derive them in every workgroup of every launch (an integer division for the strip, two 64-bit ones for the even row
+// split, two 64-bit modulos per lane for the wrapped columns).  The planner builds them once, one
+// 32-byte record per dispatch slot T of a member (the slot's entry of the tile list when fully masked tiles are skipped,
+// the identity -- or the seam launch's heavy-first order -- otherwise), and the kernel takes its record with one scalar load.
+struct PipeTileRec {
+    int wt;                    // tile id (xinv_tile_rows); -1: an idle slot (the member has fewer active tiles than slots)
+    int strip;
+    int yu0, yu1;              // owned rows [yu0, yu1)
+    int gtot;                  // global steps of the tile's march (xinv_pipe_gtot)
+    int c0;                    // column of lane 0's .x slot, unwrapped: first owned column - west halo (negative in strip 0)
+    int w0;                    // ... wrapped into the row [0, xc) (periodic x), into the even ring [0, xc + 1) (seam); else c0
+    int xu0;                   // first owned column
+};
+static_assert(sizeof(PipeTileRec) == 32, "one s_load_dwordx8");
+// the kernel's constants the records depend on (xinv_pipe2d.h: XINV_PIPE_*)
+struct PipeTileGeom { int H, UW, lag, b, period0, period; };
+
+// `seam`: the ring layout's strips (H + 2 / H west halo, xinv_ring_*); `per`: periodic x (always with seam).
+// wt < 0: the idle record -- tile 0's geometry (every field a valid one: the kernel forms addresses from it before it looks
+// at wt), wt = -1.
+__host__ __device__ inline PipeTileRec xinv_pipe_tile_rec(int wt, int nstrip, int nrb, int64_t yc, int RY, int64_t xc, bool per,
+                                                          bool seam, const PipeTileGeom &g)
+{
+    PipeTileRec r;
+    const TileRows t = xinv_tile_rows(wt < 0 ? 0 : wt, nstrip, nrb, yc, RY);
+    r.wt = wt < 0 ? -1 : wt;
+    r.strip = t.strip;
+    r.yu0 = (int)t.y0; r.yu1 = (int)t.y1;
+    r.gtot = xinv_pipe_gtot(r.yu1 - r.yu0, g.lag, g.b, g.period0, g.period);
+    const int UW = seam ? xinv_ring_uw(xc, g.H) : g.UW, HW = seam ? xinv_ring_hw(xc, g.H, t.strip) : g.H;
+    const int64_t xu0 = (int64_t)t.strip * UW, c0 = xu0 - HW;
+    r.xu0 = (int)xu0; r.c0 = (int)c0;
+    if (seam || per) {
+        const int64_t xv = seam ? xc + 1 : xc;
+        int64_t w = c0 % xv; if (w < 0) w += xv;
+        r.w0 = (int)w;
+    } else r.w0 = (int)c0;
+    return r;
+}
+
+// column `w0 + 2 lane` of a lane, wrapped into [0, n): w0 < n and 2 lane <= 126, so a row of 128 columns or more wraps
+// once at the most (an add and a conditional subtract); shorter rows take the 32-bit remainder
+XINV_HD_INLINE int xinv_wrap_lane_col(int w0, int lane, int n)
+{
+    int w = w0 + 2 * lane;
+    if (n >= 128) return w >= n ? w - n : w;
+    return (int)((unsigned)w % (unsigned)n);
+}
+// make_lanecols from the tile's record: the same map, field for field
+template <bool AL>
+XINV_HD_INLINE LaneCols xinv_lanecols_rec(const PipeTileRec &r, int UW, int lane, int xc, bool per)
+{
+    LaneCols lc;
+    const int c0 = r.c0 + 2 * lane, c1 = c0 + 1;
+    if (per) {
+        const int w0 = xinv_wrap_lane_col(r.w0, lane, xc), w1 = (w0 + 1 == xc) ? 0 : w0 + 1;
+        lc.l0 = w0; lc.l1 = w1;
+        lc.ok_x = lc.ok_y = true;
+        lc.cls_x = lc.cls_y = 1;
+    } else {
+        if (AL) {
+            const int p = c0 < 0 ? 0 : (c0 > xc - 2 ? xc - 2 : c0);
+            lc.l0 = p; lc.l1 = p + 1;
+        } else {
+            lc.l0 = c0 < 0 ? 0 : (c0 > xc - 1 ? xc - 1 : c0);
+            lc.l1 = c1 < 0 ? 0 : (c1 > xc - 1 ? xc - 1 : c1);
+        }
+        lc.ok_x = (c0 >= 1 && c0 <= xc - 2);
+        lc.ok_y = (c1 >= 1 && c1 <= xc - 2);
+        lc.cls_x = lc.ok_x ? 1 : (c0 == 0 ? 2 : (c0 == xc - 1 ? 3 : 0));
+        lc.cls_y = lc.ok_y ? 1 : (c1 == xc - 1 ? 3 : 0);
+    }
+    lc.use_x = (c0 >= r.xu0 && c0 < r.xu0 + UW && c0 < xc);
+    lc.use_y = (c1 >= r.xu0 && c1 < r.xu0 + UW && c1 < xc);
+    return lc;
+}
+// xinv_lanecols_ring from the tile's record
+XINV_HD_INLINE LaneCols xinv_lanecols_ring_rec(const PipeTileRec &r, int UW, int lane, int xc, bool &seam_lane)
+{
+    LaneCols lc;
+    const int c0 = r.c0 + 2 * lane, c1 = c0 + 1, xv = xc + 1;
+    const int w0 = xinv_wrap_lane_col(r.w0, lane, xv), w1 = (w0 + 1 == xv) ? 0 : w0 + 1;
+    lc.l0 = w0; lc.l1 = (w1 == xc) ? xc - 1 : w1;
+    lc.ok_x = true; lc.ok_y = (w1 != xc);
+    lc.cls_x = lc.cls_y = 1;
+    lc.use_x = (c0 >= r.xu0 && c0 < r.xu0 + UW && c0 < xc);
+    lc.use_y = (c1 >= r.xu0 && c1 < r.xu0 + UW && c1 < xc);
+    seam_lane = (w0 == xc - 1);
+    return lc;
+}
+
+// Dispatch slot T of a launch of NB workgroups <- blockIdx.x = L: workgroup L lands on XCD L & 7, and an XCD's workgroups
+// take a contiguous range of slots (the kernel's arithmetic; a bijection of [0, NB))
+__host__ __device__ inline int xinv_pipe_slot(int L, int NB)
+{
+    const int q = NB >> 3, rem = NB & 7, xcd = L & 7, idx = L >> 3;
+    return xcd * q + (xcd < rem ? xcd : rem) + idx;
+}
+// The records of a launch WITHOUT a tile list: NB = nstrip * nrb slots, every tile active.  Slot T holds tile T -- or, in
+// a seam launch, the tile of the heavy-first order (the edge strips' tiles dispatched first: xinv_heavy_first /
+// xinv_seam_tile of the workgroup's dispatch position).
+__host__ inline void xinv_pipe_identity_recs(PipeTileRec *out, int nstrip, int nrb, int64_t yc, int RY, int64_t xc, bool per,
+                                             bool seam, const PipeTileGeom &g)
+{
+    const int NB = nstrip * nrb;
+    for (int L = 0; L < NB; L++) {
+        const int T = xinv_pipe_slot(L, NB);
+        const int wt = seam ? xinv_seam_tile(xinv_heavy_first(L, NB, (nstrip == 1 ? 1 : 2) * nrb), nstrip, nrb) : T;
+        out[T] = xinv_pipe_tile_rec(wt, nstrip, nrb, yc, RY, xc, per, seam, g);
+    }
 }
 
 // ---- the planner's cost models (host only; pure integer / double arithmetic, checked on the CPU) --------------------------
