@@ -1,7 +1,8 @@
 """Fourier plans without a GPU ("Plans"): the numpy restatement of k_fourier_factor / k_fourier_subst
 (tests/fourier_plan_model.py) gives the BITS of the one-shot restatement (tests/fourier_model.py) -- the stored-factor march
-with the real and imaginary parts separated is the same sequence of float64 operations --, the C-ABI names, and the words
-with which ResidentProblem.solve_fourier refuses a batch outside the path's scope.
+with the real and imaginary parts separated is the same sequence of float64 operations --, the C-ABI names, the argument checks
+of the plan entries, of the four one-shot entries and of xinv_rowdft_f64_dev (all answered before any device call), and the
+words with which ResidentProblem.solve_fourier refuses a batch outside the path's scope.
 """
 import inspect
 import os
@@ -139,6 +140,144 @@ def test_the_entries_refuse_a_dead_plan_and_bad_arguments_before_any_device_call
     assert L.xinv_fourier_plan_create_standard_2d_f64_dev(ctypes.byref(h), None, one, 1, _lib.strides_arg([0, 0]), 5, 12, 1.0,
                                                           1.0, U, None) == -1 and 'null array' in err()
     assert h.value is None
+
+
+# ------------------------------------------------------------------ the one-shot entries and the row transform
+# Every refusal below is answered before the first device call: the device addresses are dummies that are never
+# dereferenced, the host arrays of the _batched entries are small.  (nper: the per-row coefficient arrays between S and the
+# forcing; letters: how the stride rule names them.)
+FORMS = {'standard': (2, 'A, C', 'A and C', 2), 'general': (5, 'A, C, D, E, F', 'A, C, D, E and F', 4)}
+STRIDE_RULE = 'batch stride must be 0 (shared; not S) or at least one member (%s: one value per row)'
+LDS = "the row length 4500 is beyond the transform's LDS budget (at most 4096 points)"
+PRIME = 'the row length 14 has the prime factor 7 (the transform takes products of 2, 3 and 5)'
+
+
+def _strides(nper, yc, xc, **over):
+    st = [yc * xc] + [yc] * nper + [yc * xc]
+    for k, v in over.items():
+        st[{'S': 0, 'coef': 1, 'last_coef': nper, 'forcing': nper + 1}[k]] = v
+    return st
+
+
+# name -> (keyword arguments of `dev_entry`, the message); the later cases are wrong in two ways and report the earlier one
+DEV_REFUSED = {
+    'null coefficient': (dict(null=1), 'null array'),
+    'null forcing': (dict(null=-1), 'null array'),
+    'null S': (dict(null=0), 'null array'),
+    'null strides': (dict(no_strides=True), 'null strides'),
+    'nbatch = 0': (dict(nb=0), 'nbatch < 1'),
+    'yc = 2': (dict(yc=2), 'every core dimension needs at least 3 points'),
+    'negative stride': (dict(nb=2, over=dict(coef=-1)), 'negative batch stride'),
+    'S shared': (dict(nb=2, over=dict(S=0)), STRIDE_RULE),
+    'S too close': (dict(nb=2, over=dict(S=5 * 12 - 1)), STRIDE_RULE),
+    'coefficient too close': (dict(nb=2, over=dict(last_coef=5 - 1)), STRIDE_RULE),
+    'forcing too close': (dict(nb=2, over=dict(forcing=5 * 12 - 1)), STRIDE_RULE),
+    'xc = 14': (dict(xc=14), PRIME),
+    'xc = 4500': (dict(xc=4500), LDS),
+    'null array before null strides': (dict(null=1, no_strides=True), 'null array'),
+    'null strides before nbatch': (dict(no_strides=True, nb=0), 'null strides'),
+    'core dimension before the strides': (dict(nb=2, yc=2, over=dict(coef=-1)), 'every core dimension needs at least 3 points'),
+    'stride rule before the row length': (dict(nb=2, xc=14, over=dict(S=0)), STRIDE_RULE),
+}
+
+
+def dev_entry(L, form, nb=1, yc=5, xc=12, null=None, no_strides=False, over={}):
+    import ctypes
+    nper = FORMS[form][0]
+    arrays = [ctypes.c_void_p(8)] * (nper + 2)
+    if null is not None:
+        arrays[null] = None
+    flags = np.zeros((max(nb, 1), 3))
+    st = None if no_strides else _lib.strides_arg(_strides(nper, yc, xc, **over))
+    fn = getattr(L, 'xinv_fourier_%s_2d_f64_dev' % form)
+    return fn(*arrays, nb, st, yc, xc, *([1.0] * FORMS[form][3]), U, _lib.hptr(flags), None)
+
+
+@pytest.mark.parametrize('name', list(DEV_REFUSED))
+@pytest.mark.parametrize('form', list(FORMS))
+def test_the_device_entries_refuse_bad_arguments_before_any_device_call(form, name):
+    kw, msg = DEV_REFUSED[name]
+    L = _lib.load()
+    assert dev_entry(L, form, **kw) == -1
+    err = L.xinv_last_error().decode()
+    assert err == 'xinv_fourier: ' + (msg % FORMS[form][1] if '%s' in msg else msg)
+
+
+@pytest.mark.parametrize('form', list(FORMS))
+def test_a_valid_device_call_gets_as_far_as_the_device(form):
+    """Past the checks the entry asks HIP for the current device: without one that is XINV_ERR_HIP (-2), not an argument
+    error.  (With a device the dummy addresses would be read: the call is made only where there is none.)"""
+    L = _lib.load()
+    if L.xinv_device_count() >= 1:
+        pytest.skip('a device is present: the call would read the dummy addresses')
+    assert dev_entry(L, form) == -2
+    assert dev_entry(L, form, nb=2) == -2
+
+
+def host_entry(L, form, nb=1, yc=5, xc=12, over={}, **opt):
+    nper = FORMS[form][0]
+    arrays = [np.ones((nb, yc, xc))] + [np.ones((nb, yc))] * nper + [np.ones((nb, yc, xc))]
+    flags = np.zeros((nb, 3))
+    fn = getattr(L, 'xinv_fourier_%s_2d_f64_batched' % form)
+    return fn(*[_lib.hptr(a) for a in arrays], nb, _lib.strides_arg(_strides(nper, yc, xc, **over)), yc, xc,
+              *([1.0] * FORMS[form][3]), U, _lib.hptr(flags), _lib.options(**opt))
+
+
+MASKS = 'float64 arrays only, %s one value per row (f32_mask, prep_flags and rowconst_mask must be 0)'
+HOST_REFUSED = {
+    'ndev = 2': (dict(devices=[0, 1]), 'one device only (xinv_options.ndev must be 0 or 1)'),
+    'f32_mask': (dict(f32_mask=1), MASKS),
+    'rowconst_mask': (dict(rowconst_mask=2), MASKS),
+    'xc = 14': (dict(xc=14), PRIME),
+    'the arguments before the options': (dict(nb=2, over=dict(S=0), devices=[0, 1]), STRIDE_RULE),
+    'ndev before the masks': (dict(devices=[0, 1], f32_mask=1), 'one device only (xinv_options.ndev must be 0 or 1)'),
+    'the masks before the row length': (dict(f32_mask=1, xc=14), MASKS),
+}
+
+
+@pytest.mark.parametrize('name', list(HOST_REFUSED))
+@pytest.mark.parametrize('form', list(FORMS))
+def test_the_host_entries_refuse_options_and_the_row_length_before_asking_for_a_device(form, name):
+    kw, msg = HOST_REFUSED[name]
+    L = _lib.load()
+    assert host_entry(L, form, **kw) == -1                    # (XINV_ERR_ARG, also where there is no device)
+    err = L.xinv_last_error().decode()
+    assert err == 'xinv_fourier: ' + (msg % FORMS[form][2 if msg is MASKS else 1] if '%s' in msg else msg)
+
+
+@pytest.mark.parametrize('form', list(FORMS))
+def test_a_valid_host_call_without_a_device_is_nodev(form):
+    L = _lib.load()
+    if L.xinv_device_count() >= 1:
+        pytest.skip('a device is present: the call would be a solve, not XINV_ERR_NODEV')
+    assert host_entry(L, form, nb=2) == -3
+    assert L.xinv_last_error().decode() == 'no HIP device available'
+
+
+ROWDFT_REFUSED = {
+    'null out': (dict(out=None), 'null array'),
+    'null in': (dict(inp=None), 'null array'),
+    'in place': (dict(inp=8), 'the transform is not in place'),
+    'nrows = 0': (dict(nrows=0), 'nrows < 1'),
+    'n = 1': (dict(n=1), 'a row needs at least 2 points, got 1'),
+    'n = 14': (dict(n=14), PRIME),
+    'n = 8192': (dict(n=8192), "the row length 8192 is beyond the transform's LDS budget (at most 4096 points)"),
+    'null before in place': (dict(out=None, inp=None), 'null array'),
+    'in place before nrows': (dict(inp=8, nrows=0), 'the transform is not in place'),
+    'nrows before the row length': (dict(nrows=0, n=14), 'nrows < 1'),
+}
+
+
+@pytest.mark.parametrize('inverse', [0, 1])
+@pytest.mark.parametrize('name', list(ROWDFT_REFUSED))
+def test_the_row_transform_refuses_bad_arguments_before_any_device_call(name, inverse):
+    import ctypes
+    kw, msg = ROWDFT_REFUSED[name]
+    a = dict(dict(out=8, inp=4096, nrows=3, n=12), **kw)
+    ptr = lambda v: None if v is None else ctypes.c_void_p(v)
+    L = _lib.load()
+    assert L.xinv_rowdft_f64_dev(ptr(a['out']), ptr(a['inp']), a['nrows'], a['n'], inverse, None) == -1
+    assert L.xinv_last_error().decode() == 'xinv_fourier: ' + msg
 
 
 # ------------------------------------------------------------------ ResidentProblem.solve_fourier: the refusals

@@ -181,15 +181,15 @@ def _method(kind, iParams):
     if method not in ('sor', 'direct', 'fourier', 'cfourier'):
         raise Exception("iParams['method'] must be 'sor' or 'direct' (or 'fourier', for inv_standard2D; or 'cfourier', for "
                         "inv_general2D), got %r" % (method,))
-    if method == 'cfourier' and kind != 'gen2d':
-        raise Exception("iParams['method'] = 'cfourier' is available for the 2-D general form only (inv_general2D and the "
-                        "apps on it), not for %s; 'sor' solves this case" % forms.FORMS[kind].inv)
     if method == 'direct' and kind != 'std1d':
         raise Exception("iParams['method'] = 'direct' is available for the 1-D standard form only (inv_standard1D, "
                         "invert_GeoAdjustment, invert_RefStateSWM), not for %s" % forms.FORMS[kind].inv)
-    if method == 'fourier' and kind != 'std2d':
-        raise Exception("iParams['method'] = 'fourier' is available for the 2-D standard form only (inv_standard2D and the "
-                        "apps on it), not for %s; 'sor' solves this case" % forms.FORMS[kind].inv)
+    if method in ('fourier', 'cfourier'):
+        from . import fourier
+        own = forms.FORMS[fourier.METHODS[method]['kind']]
+        if kind != own.kind:
+            raise Exception("iParams['method'] = '%s' is available for the 2-D %s form only (%s and the apps on it), not for "
+                            "%s; 'sor' solves this case" % (method, own.name.split('_')[0], own.inv, forms.FORMS[kind].inv))
     return method
 
 
@@ -425,16 +425,18 @@ def _residual(kind, coefs, F, S, dims, iParams):
     return F.like(np.ascontiguousarray(out), 'residual')
 
 
-def _solve_fourier(coefs, F, S, dims, iParams):
-    """iParams['method'] = 'fourier': one call of xinv_fourier_standard_2d_f64_batched on every slice (float64; the forcing
-    built on the host; A and C travel as one value per row).  optArg, mxLoop and tolerance play no part; flags =
-    [overflow, 0, 0].  A call outside the path's scope raises before anything runs (fourier.eligible)."""
+def _solve_fourier(method, coefs, F, S, dims, iParams):
+    """iParams['method'] = 'fourier' / 'cfourier': one call of the method's host-pointer entry (fourier.METHODS) on every
+    slice (float64; the forcing built on the host; the coefficients travel as one value per row).  optArg, mxLoop and
+    tolerance play no part; flags = [overflow, 0, 0].  A call outside the path's scope raises before anything runs
+    (fourier.eligible_for)."""
     from . import fourier
+    how = fourier.METHODS[method]
     if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
         raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
     devs = iParams.get('devices')
     if devs is not None and (isinstance(devs, str) or len(list(devs)) > 1):
-        raise NotImplementedError("iParams['method'] = 'fourier' runs on one device: name it with iParams['device']")
+        raise NotImplementedError("iParams['method'] = '%s' runs on one device: name it with iParams['device']" % method)
     perm, bdims, bshape = _batch_layout(F, dims)
     core_shape = tuple(F.shape[F.axis(d)] for d in dims)
     nbatch = int(np.prod(bshape)) if bshape else 1
@@ -446,15 +448,16 @@ def _solve_fourier(coefs, F, S, dims, iParams):
         S = F.like(np.zeros(F.shape))
     tr = lambda v: np.ascontiguousarray(np.transpose(np.asarray(v, dtype=np.float64), perm)).reshape((nbatch,) + core_shape)
     Fv, Sv = tr(F.values), tr(S.values)
-    A, B, C = [_prep_coef(c, F, perm, core_shape, nbatch, allow_null=(k == 1)) for k, c in enumerate(coefs)]
-    Ar, Cr = fourier.eligible((A[0], A[2]), (B[0], B[2]), (C[0], C[2]), Fv, Sv, iParams['BCs'], _undeftmp)
+    cs = [_prep_coef(c, F, perm, core_shape, nbatch, allow_null=(k == 1)) for k, c in enumerate(coefs)]
+    B = cs.pop(1)
+    rows = fourier.eligible_for(method, {k: (c[0], c[2]) for k, c in zip(how['coefs'], cs)}, (B[0], B[2]), Fv, Sv,
+                                iParams['BCs'], _undeftmp)
     L = _lib.require_gpu()
-    strides = [n, yc if Ar.ndim == 2 else 0, yc if Cr.ndim == 2 else 0, n]
+    strides = [n] + [yc if r.ndim == 2 else 0 for r in rows] + [n]
     flags = np.zeros((nbatch, 3))
-    rc = L.xinv_fourier_standard_2d_f64_batched(_lib.hptr(Sv), _lib.hptr(Ar), _lib.hptr(Cr), _lib.hptr(Fv), nbatch,
-                                                _lib.strides_arg(strides), yc, xc, float(iParams['del1Sqr']),
-                                                float(iParams['ratioSqr']), _undeftmp, _lib.hptr(flags),
-                                                _lib.options(device=int(iParams.get('device', -1))))
+    rc = getattr(L, how['entry'])(_lib.hptr(Sv), *[_lib.hptr(r) for r in rows], _lib.hptr(Fv), nbatch, _lib.strides_arg(strides),
+                                yc, xc, *[float(iParams[k]) for k in how['scalars']], _undeftmp, _lib.hptr(flags),
+                                _lib.options(device=int(iParams.get('device', -1))))
     _lib.check(rc)
     out = np.transpose(Sv.reshape(tuple(bshape) + core_shape), np.argsort(perm))
     if S.values.dtype == out.dtype and S.values.flags.writeable:
@@ -470,57 +473,10 @@ def _solve_fourier(coefs, F, S, dims, iParams):
     return S
 
 
-def _solve_cfourier(coefs, G, S, dims, iParams):
-    """iParams['method'] = 'cfourier': one call of xinv_fourier_general_2d_f64_batched on every slice (float64; the forcing
-    built on the host; A, C, D, E and F travel as one value per row).  optArg, mxLoop and tolerance play no part; flags =
-    [overflow, 0, 0].  A call outside the path's scope raises before anything runs (fourier.eligible_general)."""
-    from . import fourier
-    if not isinstance(G, Field) or not (isinstance(S, Field) or S is None):
-        raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')
-    devs = iParams.get('devices')
-    if devs is not None and (isinstance(devs, str) or len(list(devs)) > 1):
-        raise NotImplementedError("iParams['method'] = 'cfourier' runs on one device: name it with iParams['device']")
-    perm, bdims, bshape = _batch_layout(G, dims)
-    core_shape = tuple(G.shape[G.axis(d)] for d in dims)
-    nbatch = int(np.prod(bshape)) if bshape else 1
-    yc, xc = core_shape
-    n = yc * xc
-    if nbatch == 0:
-        return S if S is not None else G.like(np.zeros(G.shape))
-    if S is None:
-        S = G.like(np.zeros(G.shape))
-    tr = lambda v: np.ascontiguousarray(np.transpose(np.asarray(v, dtype=np.float64), perm)).reshape((nbatch,) + core_shape)
-    Gv, Sv = tr(G.values), tr(S.values)
-    cs = [_prep_coef(c, G, perm, core_shape, nbatch, allow_null=(k == 1)) for k, c in enumerate(coefs)]
-    rows = fourier.eligible_general(*[(c[0], c[2]) for c in cs], Gv, Sv, iParams['BCs'], _undeftmp)
-    L = _lib.require_gpu()
-    strides = [n] + [yc if r.ndim == 2 else 0 for r in rows] + [n]
-    flags = np.zeros((nbatch, 3))
-    rc = L.xinv_fourier_general_2d_f64_batched(_lib.hptr(Sv), *[_lib.hptr(r) for r in rows], _lib.hptr(Gv), nbatch,
-                                               _lib.strides_arg(strides), yc, xc, float(iParams['del1']),
-                                               float(iParams['del1Sqr']), float(iParams['ratio']), float(iParams['ratioSqr']),
-                                               _undeftmp, _lib.hptr(flags), _lib.options(device=int(iParams.get('device', -1))))
-    _lib.check(rc)
-    out = np.transpose(Sv.reshape(tuple(bshape) + core_shape), np.argsort(perm))
-    if S.values.dtype == out.dtype and S.values.flags.writeable:
-        S.values[...] = out
-    else:
-        S.values = np.ascontiguousarray(out)
-    iParams['flags'] = flags if nbatch > 1 else flags[0]
-    iParams['stats'] = _lib.last_stats()
-    if iParams.get('printInfo', True):
-        coords = [np.asarray(G[d]) for d in bdims]
-        for m, idx in enumerate(itertools.product(*coords) if bdims else [()]):
-            print(_info(dict(zip(bdims, idx))) + ' fourier solve' + (' (overflows!)' if flags[m, 0] else ''))
-    return S
-
-
 def _solve(kind, coefs, F, S, dims, iParams):
     method = _method(kind, iParams)
-    if method == 'fourier':
-        return _solve_fourier(coefs, F, S, dims, iParams)
-    if method == 'cfourier':
-        return _solve_cfourier(coefs, F, S, dims, iParams)
+    if method in ('fourier', 'cfourier'):
+        return _solve_fourier(method, coefs, F, S, dims, iParams)
     direct = method == 'direct'
     if not isinstance(F, Field) or not (isinstance(S, Field) or S is None):
         raise Exception('forcing and solution must be Field objects (see xinvert_amd.field)')

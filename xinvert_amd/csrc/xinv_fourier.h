@@ -384,6 +384,20 @@ __global__ void __launch_bounds__(XINV_FCHK_WG) k_fourier_check(FourierCheckArgs
 
 #endif /* XINV_FOURIER_KERNELS */
 
+// The launch loop of every kernel of this family (and of xinv_cfourier.h) that takes a member, or a coefficient set, per
+// blockIdx.y: one launch per chunk, with the chunk's first member in the arguments' `first` field (member0 / set0).
+#define FOURIER_MEMBER_CHUNK 32768       /* members per launch (grid.y <= 65535) */
+template <class Args>
+static inline void xinv_launch_chunks(void (*kernel)(Args), Args a, int64_t Args::*first, int64_t members, unsigned gx,
+                                      unsigned wg, hipStream_t st)
+{
+    for (int64_t m0 = 0; m0 < members; m0 += FOURIER_MEMBER_CHUNK) {
+        const int64_t nm = members - m0 < FOURIER_MEMBER_CHUNK ? members - m0 : FOURIER_MEMBER_CHUNK;
+        a.*first = m0;
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)nm), dim3(wg), 0, st, a);
+    }
+}
+
 // xinv_tu_fourier.hip
 __attribute__((visibility("hidden"))) int xinv_launch_rowdft(const RowDftArgs &a, bool inverse, hipStream_t st);
 __attribute__((visibility("hidden"))) void xinv_launch_fourier_tri(FourierTriArgs a, int64_t nbatch, hipStream_t st);

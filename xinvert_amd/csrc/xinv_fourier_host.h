@@ -1,16 +1,30 @@
-// xinv_fourier_host.h -- host side of the direct Fourier solve (xinv_fourier.h): the factorisation of the row length, the
-// per-device tables (twiddles, lambda) and workspace, the argument checks of xinv_fourier_standard_2d_f64_dev / _batched and
-// of xinv_rowdft_f64_dev, the host-pointer staging, and the plans (xinv_fourier_plan_*: factor once, solve many).  Included by
-// xinv_hip.hip only.
+// xinv_fourier_host.h -- host side of the direct Fourier solves (xinv_fourier.h, xinv_cfourier.h): the factorisation of the
+// row length, the per-device tables (twiddles, lambda, sigma), xinv_rowdft_f64_dev, and the one pipeline behind the one-shot
+// entries of both forms and the plans -- the call and its argument checks (fourier_validate), the three transforms
+// (fourier_dfts), the steps of a one-shot solve around the form's own kernels (fourier_open, fourier_checked,
+// fourier_close), the standard form's solve, the device and host-pointer entries of both forms (fourier_dev, fourier_host)
+// and the plans (xinv_fourier_plan_*: factor once, solve many).  Included by xinv_hip.hip only.
 #pragma once
 #include "xinv_fourier.h"
 
+// One array of a call, as the checks and the staging see it.
+struct FourierArr {
+    double *p;                           // (only S is written)
+    int64_t len;                         // doubles per member: yc * xc, or yc for a coefficient (one value per row)
+    int64_t stride;                      // batch stride in elements; 0 = shared (not S)
+};
+
+// One call of either one-shot form (mk_fourier of xinv_hip.hip fills it).
 struct FourierCall {
-    double *S;
-    const double *A, *C, *F;
+    FourierArr a[7];                     // the ABI's order: S, the coefficients (A, C / A, C, D, E, Fc), the forcing (F / G)
+    int na;                              // 4 / 7
+    const char *letters, *letters_and;   // the coefficients as the messages name them: "A, C" and "A and C"
     int64_t nbatch, yc, xc;
-    int64_t s[4];                        // batch strides of S, A, C, F (elements; 0 = shared, not S)
-    double delxSqr, ratioSqr, undef;
+    double delx, delxSqr, ratio, ratioSqr, undef;       // (the standard form: delxSqr, ratioSqr, undef)
+    double *S() const { return a[0].p; }
+    const double *coef(int q) const { return a[1 + q].p; }
+    const double *forcing() const { return a[na - 1].p; }
+    int64_t stride(int q) const { return nbatch > 1 ? a[q].stride : 0; }      // as the kernels take it: one member has none
 };
 
 static int fourier_fail(const std::string &what)
@@ -109,133 +123,207 @@ static int rowdft_dev(double *out, const double *in, int64_t nrows, int64_t n, i
     return fourier_rowdft(a, inverse != 0, st);
 }
 
-static int fourier_validate(const FourierCall &c, const int64_t *strides, const double *flags)
+// The argument checks of every entry that takes arrays with batch strides: the one-shot forms (S, the coefficients, the
+// forcing), a plan's create (A, C) and its solve (S, F).  `own0`: a[0] is S, which no two members share; `strides`: the
+// caller passed its array of strides (a plan's solve takes them as two scalars: true); `letters`: the form's coefficients,
+// as the stride rule names them.
+static int fourier_validate(const FourierArr *a, int na, bool own0, bool strides, int64_t nbatch, int64_t yc, int64_t xc,
+                            const char *letters)
 {
-    if (!c.S || !c.A || !c.C || !c.F || !flags) return fourier_fail("null array");
+    for (int q = 0; q < na; q++)
+        if (!a[q].p) return fourier_fail("null array");
     if (!strides) return fourier_fail("null strides");
-    if (c.nbatch < 1) return fourier_fail("nbatch < 1");
-    if (c.yc < 3 || c.xc < 3) return fourier_fail("every core dimension needs at least 3 points");
-    const int64_t n = c.yc * c.xc;
-    const int64_t need[4] = { n, c.yc, c.yc, n };
-    for (int q = 0; q < 4; q++) {
-        if (c.s[q] < 0) return fourier_fail("negative batch stride");
-        if (c.nbatch > 1 && c.s[q] < need[q] && !(q > 0 && c.s[q] == 0))
-            return fourier_fail("batch stride must be 0 (shared; not S) or at least one member (A, C: one value per row)");
+    if (nbatch < 1) return fourier_fail("nbatch < 1");
+    if (yc < 3 || xc < 3) return fourier_fail("every core dimension needs at least 3 points");
+    for (int q = 0; q < na; q++) {
+        if (a[q].stride < 0) return fourier_fail("negative batch stride");
+        if (nbatch > 1 && a[q].stride < a[q].len && !(a[q].stride == 0 && !(own0 && q == 0)))
+            return fourier_fail(std::string("batch stride must be 0 (shared; not S) or at least one member (") + letters +
+                                ": one value per row)");
     }
     return XINV_OK;
 }
 
-// Device arrays, on `st`, with the device already selected.  The spectrum and the forward factors live in the workspace's one
-// buffer: the device's lock covers the call, the event covers what the call leaves queued when it returns early with an
-// error; the next user of the buffer -- on any stream -- is ordered behind it, or waits on the host before the buffer grows.
-static int fourier_run_dev(const FourierCall &c, double *flags, hipStream_t st)
+// The three transforms of a solve: forward, F * delxSqr on rows 1 .. yc-2 and S on rows 0 and yc-1 into the spectrum
+// [nb][yc][K] complex; inverse, rows 1 .. yc-2 of the spectrum back to S.  `base`: the radices, the table and the row
+// length; `skip`: null, or a word per member (RowDftArgs::skip) for the inverse.
+struct FourierDfts { RowDftArgs fwdF, fwdS, inv; };
+
+static FourierDfts fourier_dfts(const RowDftArgs &base, double *spec, double *S, const double *F, int64_t sS, int64_t sF,
+                                int64_t nb, int64_t yc, int64_t xc, double delxSqr, const int *skip)
 {
-    RowDftArgs d;
-    memset(&d, 0, sizeof d);
-    int rc = fourier_factor(c.xc, d.radix, &d.npass);
-    if (rc) return rc;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    Workspace *ws = get_ws(device);
-    std::lock_guard<std::recursive_mutex> lock(ws->busy);
-    const int64_t nb = c.nbatch, yc = c.yc, xc = c.xc, K = xc / 2 + 1, plane = yc * K;
-    const size_t need = (size_t)nb * (size_t)plane * 3 * sizeof(double);
-    if ((rc = ws->four_user.wait(st, !ws->four || ws->four_cap < need))) return rc;
-    if ((rc = ensure_dev(&ws->four, &ws->four_cap, need))) return rc;
-    if ((rc = ensure_dev(&ws->four_cnt, &ws->four_cnt_cap, (size_t)nb * 2 * sizeof(int)))) return rc;
-    if ((rc = ensure_pinned(&ws->h_four_cnt, &ws->h_four_cnt_cap, (size_t)nb * 2 * sizeof(int), hipHostMallocDefault))) return rc;
-    const double *tab = nullptr;
-    if ((rc = fourier_tables(ws, xc, &tab))) return rc;
-    memset(&t_stats, 0, sizeof t_stats);
-    const int64_t sS = nb > 1 ? c.s[0] : 0, sA = nb > 1 ? c.s[1] : 0, sC = nb > 1 ? c.s[2] : 0, sF = nb > 1 ? c.s[3] : 0;
-    double *spec = ws->four, *gam = ws->four + (size_t)nb * plane * 2;
-    int *bad = ws->four_cnt, *ovf = ws->four_cnt + nb;
-
-    // 1. the check pass, before anything is written
-    HIPCHK(hipMemsetAsync(ws->four_cnt, 0, (size_t)nb * 2 * sizeof(int), st));
-    FourierCheckArgs k;
-    memset(&k, 0, sizeof k);
-    k.S = c.S; k.A = c.A; k.C = c.C; k.F = c.F;
-    k.sS = sS; k.sA = sA; k.sC = sC; k.sF = sF;
-    k.yc = yc; k.xc = xc; k.undef = c.undef; k.bad = bad;
-    xinv_launch_fourier_check(k, nb, st);
-    HIPCHK(hipGetLastError());
-    if ((rc = ws->four_user.mark(st))) return rc;
-    HIPCHK(hipMemcpyAsync(ws->h_four_cnt, bad, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ws->four_user.pending = false;
-    for (int64_t m = 0; m < nb; m++)
-        if (ws->h_four_cnt[m])
-            return fourier_fail("member " + std::to_string(m) + " holds undef at " + std::to_string(ws->h_four_cnt[m]) +
-                                " of the points the solve reads (F, A, C on the interior rows, S on rows 0 and yc-1): "
-                                "a masked problem is for the sweeps");
-
-    // 2. forward transforms: F * delxSqr on rows 1 .. yc-2, S on rows 0 and yc-1
-    hipEvent_t e0 = ws->ev0[0], e1 = ws->ev1[0];
-    const bool timing = e0 && e1;
-    if (timing) HIPCHK(hipEventRecord(e0, st));
-    d.tw = tab; d.n = (int)xc;
+    const int64_t K = xc / 2 + 1, plane = yc * K;
+    FourierDfts t;
+    RowDftArgs &d = t.fwdF, &e = t.fwdS;
+    d = base;
     d.spec = spec; d.s_member = 2 * plane; d.s_first = 2 * K; d.s_step = 2 * K;
-    d.real = const_cast<double *>(c.F); d.r_member = sF; d.r_first = xc; d.r_step = xc;
-    d.rpm = yc - 2; d.nrows = nb * (yc - 2); d.scale = c.delxSqr;
-    if ((rc = fourier_rowdft(d, false, st))) return rc;
-    RowDftArgs e = d;
-    e.real = c.S; e.r_member = sS; e.r_first = 0; e.r_step = (yc - 1) * xc;
+    d.real = const_cast<double *>(F); d.r_member = sF; d.r_first = xc; d.r_step = xc;
+    d.rpm = yc - 2; d.nrows = nb * (yc - 2); d.scale = delxSqr;
+    e = d;
+    e.real = S; e.r_member = sS; e.r_first = 0; e.r_step = (yc - 1) * xc;
     e.s_first = 0; e.s_step = 2 * (yc - 1) * K;
     e.rpm = 2; e.nrows = nb * 2; e.scale = 1.0;
-    if ((rc = fourier_rowdft(e, false, st))) return rc;
+    t.inv = d;
+    t.inv.real = S; t.inv.r_member = sS; t.inv.skip = skip;
+    return t;
+}
 
-    // 3. one tridiagonal system per wavenumber
-    FourierTriArgs t;
-    memset(&t, 0, sizeof t);
-    t.spec = spec; t.gam = gam; t.A = c.A; t.C = c.C; t.lam = tab + 2 * xc;
-    t.sA = sA; t.sC = sC; t.yc = yc; t.K = K; t.ratioSqr = c.ratioSqr; t.ovf = ovf;
-    xinv_launch_fourier_tri(t, nb, st);
-    HIPCHK(hipGetLastError());
+static int fourier_forward(FourierDfts &t, hipStream_t st)
+{
+    const int rc = fourier_rowdft(t.fwdF, false, st);
+    return rc ? rc : fourier_rowdft(t.fwdS, false, st);
+}
 
-    // 4. back to rows 1 .. yc-2 of S
-    d.real = c.S; d.r_member = sS;
-    if ((rc = fourier_rowdft(d, true, st))) return rc;
-    if (timing) HIPCHK(hipEventRecord(e1, st));
-    if ((rc = ws->four_user.mark(st))) return rc;
-    HIPCHK(hipMemcpyAsync(ws->h_four_cnt, ovf, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    ws->four_user.pending = false;                       // (`st` has drained)
+// flags[m] = {overflow, 0, 0} from the members' overflow words on the host
+static void fourier_flags(double *flags, const int *ovf, int64_t nb)
+{
     for (int64_t m = 0; m < nb; m++) {
-        flags[3 * m] = ws->h_four_cnt[m] ? 1.0 : 0.0;
+        flags[3 * m] = ovf[m] ? 1.0 : 0.0;
         flags[3 * m + 1] = 0.0;
         flags[3 * m + 2] = 0.0;
     }
+}
+
+// ------------------------------------------------------------------ the one-shot solves on device arrays
+// A one-shot solve of either form is fourier_open, the form's check kernel, fourier_checked, the form's own kernels around
+// fourier_forward and the inverse transform, fourier_close.  The spectrum and the form's factors live in the workspace's one
+// buffer: the device's lock covers the call, the event covers what the call leaves queued when it returns early with an
+// error; the next user of the buffer -- on any stream -- is ordered behind it, or waits on the host before the buffer grows.
+struct FourierRun {
+    Workspace *ws = nullptr;
+    std::unique_lock<std::recursive_mutex> lock;         // the device's, to the end of the solve
+    RowDftArgs dft;                      // radices, table, row length: what the solve's transforms share
+    const double *tab = nullptr;         // twiddles [xc] complex, lambda [K], sigma [K]
+    double *spec = nullptr, *rest = nullptr;             // the spectrum [nbatch][yc][K] complex; behind it, what the form asked for
+    int *bad = nullptr, *ovf = nullptr;  // undef counts [nbatch], overflow words [nbatch]: zeroed
+    bool timing = false;
+};
+
+// With the device already selected: the row length's radices, the workspace behind its last user with `rest` doubles behind
+// the spectrum, the tables, the status words zeroed on `st`.
+static int fourier_open(FourierRun &r, const FourierCall &c, size_t rest, hipStream_t st)
+{
+    memset(&r.dft, 0, sizeof r.dft);
+    int rc = fourier_factor(c.xc, r.dft.radix, &r.dft.npass);
+    if (rc) return rc;
+    int device = 0;
+    HIPCHK(hipGetDevice(&device));
+    Workspace *ws = r.ws = get_ws(device);
+    r.lock = std::unique_lock<std::recursive_mutex>(ws->busy);
+    const size_t nb = (size_t)c.nbatch, spec = nb * (size_t)(c.yc * (c.xc / 2 + 1)) * 2;
+    const size_t need = (spec + rest) * sizeof(double), words = nb * 2 * sizeof(int);
+    if ((rc = ws->four_user.wait(st, !ws->four || ws->four_cap < need))) return rc;
+    if ((rc = ensure_dev(&ws->four, &ws->four_cap, need))) return rc;
+    if ((rc = ensure_dev(&ws->four_cnt, &ws->four_cnt_cap, words))) return rc;
+    if ((rc = ensure_pinned(&ws->h_four_cnt, &ws->h_four_cnt_cap, words, hipHostMallocDefault))) return rc;
+    if ((rc = fourier_tables(ws, c.xc, &r.tab))) return rc;
+    memset(&t_stats, 0, sizeof t_stats);
+    r.dft.tw = r.tab; r.dft.n = (int)c.xc;
+    r.spec = ws->four; r.rest = ws->four + spec;
+    r.bad = ws->four_cnt; r.ovf = ws->four_cnt + nb;
+    HIPCHK(hipMemsetAsync(ws->four_cnt, 0, words, st));
+    return XINV_OK;
+}
+
+// One of the solve's two host synchronisations: `nb` status words to the pinned mirror, behind the workspace's event
+static int fourier_mirror(Workspace *ws, const int *words, int64_t nb, hipStream_t st)
+{
+    const int rc = ws->four_user.mark(st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ws->h_four_cnt, words, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ws->four_user.pending = false;                       // (`st` has drained)
+    return XINV_OK;
+}
+
+// Behind the form's check kernel, before anything is written: the undef counts, the refusal (`reads`: the arrays the solve
+// reads on the interior rows), the start of the timed span.
+static int fourier_checked(FourierRun &r, int64_t nb, const char *reads, hipStream_t st)
+{
+    Workspace *ws = r.ws;
+    HIPCHK(hipGetLastError());
+    const int rc = fourier_mirror(ws, r.bad, nb, st);
+    if (rc) return rc;
+    for (int64_t m = 0; m < nb; m++)
+        if (ws->h_four_cnt[m])
+            return fourier_fail("member " + std::to_string(m) + " holds undef at " + std::to_string(ws->h_four_cnt[m]) +
+                                " of the points the solve reads (" + reads + " on the interior rows, S on rows 0 and yc-1): "
+                                "a masked problem is for the sweeps");
+    r.timing = ws->ev0[0] && ws->ev1[0];
+    if (r.timing) HIPCHK(hipEventRecord(ws->ev0[0], st));
+    return XINV_OK;
+}
+
+// Behind the inverse transform: the end of the timed span, the overflow words, the flags and the statistics of a solve of
+// `launches` kernels.
+static int fourier_close(FourierRun &r, int64_t nb, int launches, double *flags, hipStream_t st)
+{
+    Workspace *ws = r.ws;
+    if (r.timing) HIPCHK(hipEventRecord(ws->ev1[0], st));
+    const int rc = fourier_mirror(ws, r.ovf, nb, st);
+    if (rc) return rc;
+    fourier_flags(flags, ws->h_four_cnt, nb);
     t_stats.path = XINV_PATH_FOURIER2D;
     t_stats.lanes = 1;
     t_stats.devices = 1;
-    t_stats.sweep_launches = 4;
-    if (timing) {
+    t_stats.sweep_launches = launches;
+    if (r.timing) {
         float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(hipEventElapsedTime(&ms, ws->ev0[0], ws->ev1[0]));
         t_stats.sweep_ms = ms;
     }
     return XINV_OK;
 }
 
-static int fourier_dev(const FourierCall &c, const int64_t *strides, double *flags, hipStream_t st)
+typedef int (*FourierSolve)(const FourierCall &, double *, hipStream_t);
+
+// The standard form: the workspace holds the forward factors [nbatch][yc][K] behind the spectrum
+static int fourier_run_dev(const FourierCall &c, double *flags, hipStream_t st)
 {
-    int rc = fourier_validate(c, strides, flags);
+    FourierRun r;
+    const int64_t nb = c.nbatch, yc = c.yc, xc = c.xc, K = xc / 2 + 1;
+    int rc = fourier_open(r, c, (size_t)nb * (size_t)(yc * K), st);
     if (rc) return rc;
-    return fourier_run_dev(c, flags, st);
+    FourierCheckArgs k;
+    memset(&k, 0, sizeof k);
+    k.S = c.S(); k.A = c.coef(0); k.C = c.coef(1); k.F = c.forcing();
+    k.sS = c.stride(0); k.sA = c.stride(1); k.sC = c.stride(2); k.sF = c.stride(3);
+    k.yc = yc; k.xc = xc; k.undef = c.undef; k.bad = r.bad;
+    xinv_launch_fourier_check(k, nb, st);
+    if ((rc = fourier_checked(r, nb, "F, A, C", st))) return rc;
+
+    FourierDfts d = fourier_dfts(r.dft, r.spec, c.S(), c.forcing(), k.sS, k.sF, nb, yc, xc, c.delxSqr, nullptr);
+    if ((rc = fourier_forward(d, st))) return rc;
+    FourierTriArgs t;                                    // one tridiagonal system per wavenumber
+    memset(&t, 0, sizeof t);
+    t.spec = r.spec; t.gam = r.rest; t.A = k.A; t.C = k.C; t.lam = r.tab + 2 * xc;
+    t.sA = k.sA; t.sC = k.sC; t.yc = yc; t.K = K; t.ratioSqr = c.ratioSqr; t.ovf = r.ovf;
+    xinv_launch_fourier_tri(t, nb, st);
+    HIPCHK(hipGetLastError());
+    if ((rc = fourier_rowdft(d.inv, true, st))) return rc;
+    return fourier_close(r, nb, 4, flags, st);
+}
+
+static int fourier_dev(const FourierCall &c, const int64_t *strides, double *flags, FourierSolve run, hipStream_t st)
+{
+    if (!flags) return fourier_fail("null array");
+    const int rc = fourier_validate(c.a, c.na, true, strides != nullptr, c.nbatch, c.yc, c.xc, c.letters);
+    return rc ? rc : run(c, flags, st);
 }
 
 // Host arrays: upload (a shared array once), the solve, download S -- the plain entry of the side families (PlainStage).  Of
 // the options only `device` plays a part.  On an error nothing is downloaded: the caller's S is untouched.
-static int fourier_host(const FourierCall &hc, const int64_t *strides, double *flags, const xinv_options *opt_in)
+static int fourier_host(const FourierCall &hc, const int64_t *strides, double *flags, FourierSolve run, const xinv_options *opt_in)
 {
     xinv_options o;
     fill_options(o, opt_in);
-    int rc = fourier_validate(hc, strides, flags);
+    if (!flags) return fourier_fail("null array");
+    int rc = fourier_validate(hc.a, hc.na, true, strides != nullptr, hc.nbatch, hc.yc, hc.xc, hc.letters);
     if (rc) return rc;
     if (o.ndev > 1 || o.ndev < 0) return fourier_fail("one device only (xinv_options.ndev must be 0 or 1)");
     if (o.f32_mask != 0 || o.prep_flags != 0 || o.rowconst_mask != 0)
-        return fourier_fail("float64 arrays only, A and C one value per row (f32_mask, prep_flags and rowconst_mask must be 0)");
+        return fourier_fail(std::string("float64 arrays only, ") + hc.letters_and +
+                            " one value per row (f32_mask, prep_flags and rowconst_mask must be 0)");
     {
         int radix[XINV_DFT_MAX_PASS], np = 0;
         if ((rc = fourier_factor(hc.xc, radix, &np))) return rc;          // (before anything is uploaded)
@@ -249,30 +337,24 @@ static int fourier_host(const FourierCall &hc, const int64_t *strides, double *f
     DeviceGuard dg;
     PlainStage stage;
     HIPCHK(dg.select(o.ndev == 1 ? o.device_ids[0] : o.device));
-    const int64_t nb = hc.nbatch, n = hc.yc * hc.xc;
-    const double *src[3] = { hc.A, hc.C, hc.F };
-    const int64_t len[3] = { hc.yc, hc.yc, n };
-    int64_t rows[3], total = nb * n;
-    for (int q = 0; q < 3; q++) {
-        rows[q] = (nb == 1 || hc.s[1 + q] == 0) ? 1 : nb;
-        total += rows[q] * len[q];
+    const int64_t nb = hc.nbatch;
+    int64_t rows[7], total = 0;
+    for (int q = 0; q < hc.na; q++) {
+        rows[q] = (q == 0 || (nb > 1 && hc.a[q].stride != 0)) ? nb : 1;
+        total += rows[q] * hc.a[q].len;
     }
     if ((rc = stage.open((size_t)total * sizeof(double)))) return rc;
     FourierCall c = hc;
-    c.S = stage.carve(nb * n); c.s[0] = n;
-    if ((rc = stage.up_rows(c.S, hc.S, nb, n, hc.s[0]))) return rc;
-    const double *dev[3] = {};
-    for (int q = 0; q < 3; q++) {
-        double *at = stage.carve(rows[q] * len[q]);
-        if ((rc = stage.up_rows(at, src[q], rows[q], len[q], hc.s[1 + q]))) return rc;
-        dev[q] = at;
-        c.s[1 + q] = rows[q] > 1 ? len[q] : 0;
+    for (int q = 0; q < hc.na; q++) {
+        const int64_t len = hc.a[q].len;
+        c.a[q].p = stage.carve(rows[q] * len);
+        c.a[q].stride = (q == 0 || rows[q] > 1) ? len : 0;
+        if ((rc = stage.up_rows(c.a[q].p, hc.a[q].p, rows[q], len, hc.a[q].stride))) return rc;
     }
-    c.A = dev[0]; c.C = dev[1]; c.F = dev[2];
     stage.uploads_queued();
-    if ((rc = fourier_run_dev(c, flags, stage.st))) return rc;
+    if ((rc = run(c, flags, stage.st))) return rc;
     stage.run_done();
-    if ((rc = stage.down_rows(hc.S, c.S, nb, n, hc.s[0]))) return rc;
+    if ((rc = stage.down_rows(hc.S(), c.S(), nb, hc.a[0].len, hc.a[0].stride))) return rc;
     return stage.finish(false);
 }
 
@@ -363,19 +445,13 @@ static int fplan_create(xinv_fourier_plan **out, const double *A, const double *
 {
     if (!out) return fourier_fail("null plan");
     *out = nullptr;
-    if (!A || !C) return fourier_fail("null array");
-    if (!strides) return fourier_fail("null strides");
-    if (nbatch < 1) return fourier_fail("nbatch < 1");
-    if (yc < 3 || xc < 3) return fourier_fail("every core dimension needs at least 3 points");
-    for (int q = 0; q < 2; q++) {
-        if (strides[q] < 0) return fourier_fail("negative batch stride");
-        if (nbatch > 1 && strides[q] != 0 && strides[q] < yc)
-            return fourier_fail("batch stride must be 0 (shared; not S) or at least one member (A, C: one value per row)");
-    }
+    const FourierArr a[2] = { { const_cast<double *>(A), yc, strides ? strides[0] : 0 },
+                              { const_cast<double *>(C), yc, strides ? strides[1] : 0 } };
+    int rc = fourier_validate(a, 2, false, strides != nullptr, nbatch, yc, xc, "A, C");
+    if (rc) return rc;
     RowDftArgs d;
     memset(&d, 0, sizeof d);
-    int rc = fourier_factor(xc, d.radix, &d.npass);
-    if (rc) return rc;
+    if ((rc = fourier_factor(xc, d.radix, &d.npass))) return rc;
     int device = 0;
     HIPCHK(hipGetDevice(&device));
     const double *tab = nullptr;
@@ -405,11 +481,11 @@ static int fplan_create(xinv_fourier_plan **out, const double *A, const double *
 static int fplan_solve(xinv_fourier_plan *p, double *S, const double *F, int64_t sS, int64_t sF, hipStream_t st)
 {
     if (!p || p->magic != XINV_FPLAN_MAGIC) return fourier_fail("xinv_fourier_plan_solve_f64_dev: not a live plan");
-    if (!S || !F) return fourier_fail("null array");
     const int64_t nb = p->nbatch, yc = p->yc, xc = p->xc, K = p->K, plane = yc * K, n = yc * xc;
-    if (sS < 0 || sF < 0) return fourier_fail("negative batch stride");
-    if (nb > 1 && (sS < n || (sF != 0 && sF < n)))
-        return fourier_fail("batch stride must be 0 (shared; not S) or at least one member (A, C: one value per row)");
+    const FourierArr a[2] = { { S, n, sS }, { const_cast<double *>(F), n, sF } };
+    if (S && F && (sS < 0 || sF < 0)) return fourier_fail("negative batch stride");      // (either, before the rule on S)
+    int rc = fourier_validate(a, 2, true, true, nb, yc, xc, "A, C");
+    if (rc) return rc;
     if (nb == 1) sS = sF = 0;
     int device = 0;
     HIPCHK(hipGetDevice(&device));
@@ -419,7 +495,6 @@ static int fplan_solve(xinv_fourier_plan *p, double *S, const double *F, int64_t
     std::lock_guard<std::mutex> lock(p->mu);
     if (p->solved) HIPCHK(hipStreamWaitEvent(st, p->ev, 0));      // the spectrum and the status words are the plan's
     int *bad = p->cnt, *ovf = p->cnt + nb;
-    int rc;
     HIPCHK(hipMemsetAsync(p->cnt, 0, (size_t)nb * 2 * sizeof(int), st));
     FourierCheckArgs k;
     memset(&k, 0, sizeof k);
@@ -429,16 +504,8 @@ static int fplan_solve(xinv_fourier_plan *p, double *S, const double *F, int64_t
     xinv_launch_fourier_check(k, nb, st);
     HIPCHK(hipGetLastError());
 
-    RowDftArgs d = p->dft;
-    d.spec = p->spec; d.s_member = 2 * plane; d.s_first = 2 * K; d.s_step = 2 * K;
-    d.real = const_cast<double *>(F); d.r_member = sF; d.r_first = xc; d.r_step = xc;
-    d.rpm = yc - 2; d.nrows = nb * (yc - 2); d.scale = p->delxSqr;
-    if ((rc = fourier_rowdft(d, false, st))) return rc;
-    RowDftArgs e = d;
-    e.real = S; e.r_member = sS; e.r_first = 0; e.r_step = (yc - 1) * xc;
-    e.s_first = 0; e.s_step = 2 * (yc - 1) * K;
-    e.rpm = 2; e.nrows = nb * 2; e.scale = 1.0;
-    if ((rc = fourier_rowdft(e, false, st))) return rc;
+    FourierDfts d = fourier_dfts(p->dft, p->spec, S, F, sS, sF, nb, yc, xc, p->delxSqr, bad);
+    if ((rc = fourier_forward(d, st))) return rc;
 
     FourierSubstArgs t;
     memset(&t, 0, sizeof t);
@@ -448,8 +515,7 @@ static int fplan_solve(xinv_fourier_plan *p, double *S, const double *F, int64_t
     xinv_launch_fourier_subst(t, nb, st);
     HIPCHK(hipGetLastError());
 
-    d.real = S; d.r_member = sS; d.skip = bad;
-    if ((rc = fourier_rowdft(d, true, st))) return rc;
+    if ((rc = fourier_rowdft(d.inv, true, st))) return rc;
     HIPCHK(hipMemcpyAsync(p->h_cnt, p->cnt, (size_t)nb * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(p->ev, st));
     p->solved = true;
@@ -465,10 +531,8 @@ static int fplan_status(xinv_fourier_plan *p, double *flags, int *bad)
     if (p->solved) HIPCHK(hipEventSynchronize(p->ev));
     const int64_t nb = p->nbatch;
     int64_t first = -1;
+    fourier_flags(flags, p->h_cnt + nb, nb);
     for (int64_t m = 0; m < nb; m++) {
-        flags[3 * m] = p->h_cnt[nb + m] ? 1.0 : 0.0;
-        flags[3 * m + 1] = 0.0;
-        flags[3 * m + 2] = 0.0;
         if (bad) bad[m] = p->h_cnt[m];
         if (p->h_cnt[m] && first < 0) first = m;
     }

@@ -26,6 +26,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -517,47 +518,53 @@ int xinv_tridiag_f64_dev(double *x, const double *a, const double *b, const doub
     GUARD(tridiag_solve_dev(mk_tridiag(x, a, b, c, d, a0, cn, nbatch, strides, n), strides, (hipStream_t)stream))
 }
 
-// ---- the direct Fourier solve of the 2-D standard form for periodic x (include/xinv_fourier.h) ----------------------
-static FourierCall mk_fourier(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
-                              const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr, double undef)
+// ---- the direct Fourier solve of the 2-D standard and general forms for periodic x (include/xinv_fourier.h) --------
+// `coef`, `letters`, `letters_and`: the form's per-row coefficient arrays in the ABI's order and how the messages name them
+static FourierCall mk_fourier(double *S, std::initializer_list<const double *> coef, const double *F, const char *letters,
+                              const char *letters_and, int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc,
+                              double delx, double delxSqr, double ratio, double ratioSqr, double undef)
 {
     FourierCall c;
     memset(&c, 0, sizeof c);
-    c.S = S; c.A = A; c.C = C; c.F = F; c.nbatch = nbatch; c.yc = yc; c.xc = xc;
+    c.a[c.na++] = { S, yc * xc, 0 };
+    for (const double *p : coef) c.a[c.na++] = { const_cast<double *>(p), yc, 0 };
+    c.a[c.na++] = { const_cast<double *>(F), yc * xc, 0 };
     if (strides)
-        for (int q = 0; q < 4; q++) c.s[q] = strides[q];
-    c.delxSqr = delxSqr; c.ratioSqr = ratioSqr; c.undef = undef;
+        for (int q = 0; q < c.na; q++) c.a[q].stride = strides[q];
+    c.letters = letters; c.letters_and = letters_and;
+    c.nbatch = nbatch; c.yc = yc; c.xc = xc;
+    c.delx = delx; c.delxSqr = delxSqr; c.ratio = ratio; c.ratioSqr = ratioSqr; c.undef = undef;
     return c;
+}
+
+static FourierCall mk_fourier_std(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
+                                  const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr, double undef)
+{
+    return mk_fourier(S, { A, C }, F, "A, C", "A and C", nbatch, strides, yc, xc, 0.0, delxSqr, 0.0, ratioSqr, undef);
+}
+
+static FourierCall mk_fourier_gen(double *S, const double *A, const double *C, const double *D, const double *E, const double *F,
+                                  const double *G, int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc, double delx,
+                                  double delxSqr, double ratio, double ratioSqr, double undef)
+{
+    return mk_fourier(S, { A, C, D, E, F }, G, "A, C, D, E, F", "A, C, D, E and F", nbatch, strides, yc, xc, delx, delxSqr, ratio,
+                      ratioSqr, undef);
 }
 
 int xinv_fourier_standard_2d_f64_dev(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
                                      const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr,
                                      double undef, double *flags, void *stream)
 {
-    GUARD(fourier_dev(mk_fourier(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags,
-                      (hipStream_t)stream))
+    GUARD(fourier_dev(mk_fourier_std(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags,
+                      fourier_run_dev, (hipStream_t)stream))
 }
 
 int xinv_fourier_standard_2d_f64_batched(double *S, const double *A, const double *C, const double *F, int64_t nbatch,
                                          const int64_t *strides, int64_t yc, int64_t xc, double delxSqr, double ratioSqr,
                                          double undef, double *flags, const xinv_options *opt)
 {
-    GUARD(fourier_host(mk_fourier(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags, opt))
-}
-
-// ... of the 2-D general form (cfourier_* of xinv_cfourier_host.h)
-static CFourierCall mk_cfourier(double *S, const double *A, const double *C, const double *D, const double *E, const double *F,
-                                const double *G, int64_t nbatch, const int64_t *strides, int64_t yc, int64_t xc, double delx,
-                                double delxSqr, double ratio, double ratioSqr, double undef)
-{
-    CFourierCall c;
-    memset(&c, 0, sizeof c);
-    c.S = S; c.c[0] = A; c.c[1] = C; c.c[2] = D; c.c[3] = E; c.c[4] = F; c.G = G;
-    c.nbatch = nbatch; c.yc = yc; c.xc = xc;
-    if (strides)
-        for (int q = 0; q < 7; q++) c.s[q] = strides[q];
-    c.delx = delx; c.delxSqr = delxSqr; c.ratio = ratio; c.ratioSqr = ratioSqr; c.undef = undef;
-    return c;
+    GUARD(fourier_host(mk_fourier_std(S, A, C, F, nbatch, strides, yc, xc, delxSqr, ratioSqr, undef), strides, flags,
+                       fourier_run_dev, opt))
 }
 
 int xinv_fourier_general_2d_f64_dev(double *S, const double *A, const double *C, const double *D, const double *E,
@@ -565,8 +572,8 @@ int xinv_fourier_general_2d_f64_dev(double *S, const double *A, const double *C,
                                     int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr, double undef,
                                     double *flags, void *stream)
 {
-    GUARD(cfourier_dev(mk_cfourier(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
-                       flags, (hipStream_t)stream))
+    GUARD(fourier_dev(mk_fourier_gen(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
+                      flags, cfourier_run_dev, (hipStream_t)stream))
 }
 
 int xinv_fourier_general_2d_f64_batched(double *S, const double *A, const double *C, const double *D, const double *E,
@@ -574,8 +581,8 @@ int xinv_fourier_general_2d_f64_batched(double *S, const double *A, const double
                                         int64_t yc, int64_t xc, double delx, double delxSqr, double ratio, double ratioSqr,
                                         double undef, double *flags, const xinv_options *opt)
 {
-    GUARD(cfourier_host(mk_cfourier(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
-                        flags, opt))
+    GUARD(fourier_host(mk_fourier_gen(S, A, C, D, E, F, G, nbatch, strides, yc, xc, delx, delxSqr, ratio, ratioSqr, undef), strides,
+                       flags, cfourier_run_dev, opt))
 }
 
 int xinv_rowdft_f64_dev(double *out, const double *in, int64_t nrows, int64_t n, int inverse, void *stream)

@@ -344,7 +344,7 @@ struct Workspace {
     Behind tri_user;                                            // xinv_tridiag_f64_dev only queues its kernel, which reads and
                                                                 // writes `tri` until it ends: the next user of `tri` waits on it
     double *res_part = nullptr; size_t res_part_cap = 0;        // k_resid*: norm partials [nbatch][slots][4], then the norms [nbatch][4]
-    double *four = nullptr; size_t four_cap = 0;                // Fourier solve: spectrum [nbatch][yc][K] complex, then the forward factors [nbatch][yc][K]
+    double *four = nullptr; size_t four_cap = 0;                // Fourier solves: spectrum [nbatch][yc][K] complex, then what the form keeps (fourier_run_dev / cfourier_run_dev: its factors)
     int *four_cnt = nullptr; size_t four_cnt_cap = 0;           // ... undef counts [nbatch], then overflow words [nbatch]
     int *h_four_cnt = nullptr; size_t h_four_cnt_cap = 0;       // ... and a pinned mirror of either
     Behind four_user;                                           // ... what a call left queued on `four` (as tri_user)

@@ -3,8 +3,6 @@
 #define XINV_FOURIER_KERNELS
 #include "xinv_fourier.h"
 
-#define FOURIER_MEMBER_CHUNK 32768    /* members per launch (grid.y <= 65535) */
-
 // 0, or the HIP error of raising the kernel's dynamic-LDS limit (a pair of n complex doubles passes 64 KiB at n = 2048)
 int xinv_launch_rowdft(const RowDftArgs &a, bool inverse, hipStream_t st)
 {
@@ -23,38 +21,22 @@ int xinv_launch_rowdft(const RowDftArgs &a, bool inverse, hipStream_t st)
 void xinv_launch_fourier_tri(FourierTriArgs a, int64_t nbatch, hipStream_t st)
 {
     const unsigned gx = (unsigned)((a.K + XINV_FTRI_WG - 1) / XINV_FTRI_WG);
-    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
-        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
-        a.member0 = m0;
-        hipLaunchKernelGGL(k_fourier_tri, dim3(gx, (unsigned)nm), dim3(XINV_FTRI_WG), 0, st, a);
-    }
+    xinv_launch_chunks(k_fourier_tri, a, &FourierTriArgs::member0, nbatch, gx, XINV_FTRI_WG, st);
 }
 
 void xinv_launch_fourier_factor(FourierFactorArgs a, int64_t nset, hipStream_t st)
 {
     const unsigned gx = (unsigned)((a.K + XINV_FFAC_WG - 1) / XINV_FFAC_WG);
-    for (int64_t s0 = 0; s0 < nset; s0 += FOURIER_MEMBER_CHUNK) {
-        const int64_t ns = nset - s0 < FOURIER_MEMBER_CHUNK ? nset - s0 : FOURIER_MEMBER_CHUNK;
-        a.set0 = s0;
-        hipLaunchKernelGGL(k_fourier_factor, dim3(gx, (unsigned)ns), dim3(XINV_FFAC_WG), 0, st, a);
-    }
+    xinv_launch_chunks(k_fourier_factor, a, &FourierFactorArgs::set0, nset, gx, XINV_FFAC_WG, st);
 }
 
 void xinv_launch_fourier_subst(FourierSubstArgs a, int64_t nbatch, hipStream_t st)
 {
     const unsigned gx = (unsigned)((2 * a.K + XINV_FSUB_WG - 1) / XINV_FSUB_WG);
-    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
-        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
-        a.member0 = m0;
-        hipLaunchKernelGGL(k_fourier_subst, dim3(gx, (unsigned)nm), dim3(XINV_FSUB_WG), 0, st, a);
-    }
+    xinv_launch_chunks(k_fourier_subst, a, &FourierSubstArgs::member0, nbatch, gx, XINV_FSUB_WG, st);
 }
 
 void xinv_launch_fourier_check(FourierCheckArgs a, int64_t nbatch, hipStream_t st)
 {
-    for (int64_t m0 = 0; m0 < nbatch; m0 += FOURIER_MEMBER_CHUNK) {
-        const int64_t nm = nbatch - m0 < FOURIER_MEMBER_CHUNK ? nbatch - m0 : FOURIER_MEMBER_CHUNK;
-        a.member0 = m0;
-        hipLaunchKernelGGL(k_fourier_check, dim3((unsigned)a.yc, (unsigned)nm), dim3(XINV_FCHK_WG), 0, st, a);
-    }
+    xinv_launch_chunks(k_fourier_check, a, &FourierCheckArgs::member0, nbatch, (unsigned)a.yc, XINV_FCHK_WG, st);
 }

@@ -1,7 +1,8 @@
 """The direct Fourier solve of the 2-D standard form for periodic x (iParams['method'] = 'fourier'; include/xinv.h,
-"fourier"): the row transform for callers who want the spectrum, the eligibility test of the front end, and FourierPlan
-for callers who solve one operator again and again (the factors are kept; a solve only queues).  eligible_general is the
-eligibility test of iParams['method'] = 'cfourier', the same solve for the 2-D general form (B == 0, complex systems).
+"fourier") and of the 2-D general form (iParams['method'] = 'cfourier': B == 0, complex systems): the row transform for
+callers who want the spectrum, FourierPlan for callers who solve one operator again and again (the factors are kept; a
+solve only queues), the table of what differs between the two methods (METHODS) and the one ordered statement of their
+conditions (_conditions) behind the eligibility tests of the front end (eligible, eligible_general, resident_eligible).
 
 rfft_rows / irfft_rows are numpy.fft.rfft / irfft along the last axis of a CUDA float64 tensor, on the HIP kernel k_rowdft
 (queued on the current stream).  Row lengths are products of 2, 3 and 5 up to MAX_N.  There is no CPU fallback.
@@ -172,8 +173,40 @@ class FourierPlan:
         return self.flags, self.bad
 
 
-def _refuse(why, method='fourier'):
-    raise Exception("iParams['method'] = '%s': %s; 'sor' solves this case" % (method, why))
+# What differs between the two one-shot methods (core._method, core._solve_fourier and the eligibility tests read the rest
+# off this): the one form that has the method, the host-pointer entry, the coefficients that travel as one value per row (B, identically zero, does not), the
+# last row each is read on counted from the end (rows 1 .. yc-last), the forcing's letter, the scalars in the entry's order.
+METHODS = {
+    'fourier': dict(kind='std2d', entry='xinv_fourier_standard_2d_f64_batched', coefs='AC', last=dict(A=1, C=2), forcing='F',
+                    scalars=('del1Sqr', 'ratioSqr')),
+    'cfourier': dict(kind='gen2d', entry='xinv_fourier_general_2d_f64_batched', coefs='ACDEF', last=dict.fromkeys('ACDEF', 2),
+                     forcing='G', scalars=('del1', 'del1Sqr', 'ratio', 'ratioSqr')),
+}
+
+
+def _conditions(method, B_nonzero, BCy, BCx, varies, undef_at, yc, xc):
+    """The conditions of a Fourier path in the order of DESIGN.md 4.16; the first that fails raises an Exception naming it.
+    varies(name): whether that coefficient varies along x; undef_at(): None, or (array, rows) of the first array -- forcing,
+    coefficients, S -- with an undefined value at a point the solve reads."""
+    def no(why):
+        raise Exception("iParams['method'] = '%s': %s; 'sor' solves this case" % (method, why))
+    if B_nonzero:
+        no('B must be identically zero (the array B is not)')
+    if BCy != 'fixed':
+        no("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCy,))
+    if BCx != 'periodic':
+        no("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCx,))
+    for name in METHODS[method]['coefs']:
+        if varies(name):
+            no('%s must be constant along x (the array %s varies along it)' % (name, name))
+    at = undef_at()
+    if at:
+        no('no undefined value may sit at a point the solve reads (the array %s holds one on rows %s)' % at)
+    if yc < 3:
+        no('yc must be at least 3, got %d' % yc)
+    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
+    if err:
+        no(err)
 
 
 def resident_eligible(kind, B_nonzero, BCy, BCx, varies, yc, xc):
@@ -182,81 +215,42 @@ def resident_eligible(kind, B_nonzero, BCy, BCx, varies, yc, xc):
     device's (FourierPlan: at creation for A and C, in every solve for F and the boundary rows of S)."""
     if kind != 'std2d':
         raise _lib.XinvError("solve_fourier is available for the 2-D standard form only (kind 'std2d'), not for kind %r" % (kind,))
-    if B_nonzero:
-        _refuse('B must be identically zero (the array B is not)')
-    if BCy != 'fixed':
-        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCy,))
-    if BCx != 'periodic':
-        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCx,))
-    for name in ('A', 'C'):
-        if name in varies:
-            _refuse('%s must be constant along x (the array %s varies along it)' % (name, name))
-    if yc < 3:
-        _refuse('yc must be at least 3, got %d' % yc)
-    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
-    if err:
-        _refuse(err)
+    _conditions('fourier', B_nonzero, BCy, BCx, lambda name: name in varies, lambda: None, yc, xc)
 
 
-def _per_row(name, a, rowconst, method='fourier'):
-    """A coefficient as _prep_coef hands it over -> one float64 value per row ([yc] or [nbatch, yc])."""
-    a = np.asarray(a, dtype=np.float64)
-    if rowconst:                                         # (a stride-0 view along x: only its first column travelled)
-        return np.ascontiguousarray(a)
-    first = a[..., :1]
-    if not ((a == first) | (np.isnan(a) & np.isnan(first))).all():     # (a NaN row -- cos beyond the pole -- is constant too)
-        _refuse('%s must be constant along x (the array %s varies along it)' % (name, name), method)
-    return np.ascontiguousarray(a[..., 0])
+def eligible_for(method, coefs, B, Fv, Sv, BCs, undef):
+    """The conditions of `method` on the host arrays of one call.  coefs: {letter: (array, rowconst)} as core._prep_coef
+    returns them, and B likewise (None = identically zero); Fv (the forcing), Sv [nbatch, yc, xc].  -> the coefficients of
+    METHODS[method]['coefs'], each as one float64 value per row ([yc] or [nbatch, yc])."""
+    m = METHODS[method]
+    yc, xc = Fv.shape[-2:]
+    full = {k: np.asarray(coefs[k][0], dtype=np.float64) for k in m['coefs']}
+    # (rowconst: a stride-0 view along x, of which only the first column travelled)
+    rows = {k: np.ascontiguousarray(a if coefs[k][1] else a[..., 0]) for k, a in full.items()}
+
+    def varies(name):
+        if coefs[name][1]:
+            return False
+        a, first = full[name], full[name][..., :1]
+        return not ((a == first) | (np.isnan(a) & np.isnan(first))).all()   # (a NaN row -- cos beyond the pole -- is constant too)
+
+    def undef_at():
+        pts = [(m['forcing'], Fv[:, 1:-1], '1 .. yc-2')]
+        pts += [(k, rows[k][..., 1:yc + 1 - m['last'][k]], '1 .. yc-%d' % m['last'][k]) for k in m['coefs']]
+        pts += [('S', Sv[:, [0, -1]], '0 and yc-1')]
+        return next(((name, where) for name, p, where in pts if (p == undef).any()), None)
+
+    BCs = list(BCs)
+    _conditions(method, B[0] is not None and np.any(np.asarray(B[0]) != 0), BCs[0], BCs[1], varies, undef_at, yc, xc)
+    return [rows[k] for k in m['coefs']]
 
 
 def eligible_general(A, B, C, D, E, Fc, Gv, Sv, BCs, undef):
-    """The conditions of the Fourier path of the 2-D general form ('cfourier') on the host arrays of one call, in the order
-    of DESIGN.md 4.16, "General form"; the first that fails raises an Exception naming it.  A .. Fc: (array, rowconst) as
-    core._prep_coef returns them (B: None = identically zero); Gv, Sv [nbatch, yc, xc].  -> [A, C, D, E, Fc] as one value
-    per row.  Diagonal dominance is NOT a condition: the overflow flag and the residual are the safety net."""
-    no = lambda why: _refuse(why, 'cfourier')
-    if B[0] is not None and np.any(np.asarray(B[0]) != 0):
-        no('B must be identically zero (the array B is not)')
-    BCs = list(BCs)
-    if BCs[0] != 'fixed':
-        no("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCs[0],))
-    if BCs[1] != 'periodic':
-        no("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCs[1],))
-    rows = [_per_row(name, *c, method='cfourier') for name, c in zip('ACDEF', (A, C, D, E, Fc))]
-    pts = [('G', Gv[:, 1:-1], '1 .. yc-2')] + [(name, r[..., 1:-1], '1 .. yc-2') for name, r in zip('ACDEF', rows)] + \
-          [('S', Sv[:, [0, -1]], '0 and yc-1')]
-    for name, p, where in pts:
-        if (p == undef).any():
-            no('no undefined value may sit at a point the solve reads (the array %s holds one on rows %s)' % (name, where))
-    yc, xc = Gv.shape[-2:]
-    if yc < 3:
-        no('yc must be at least 3, got %d' % yc)
-    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
-    if err:
-        no(err)
-    return rows
+    """`eligible_for` the 2-D general form ('cfourier') -> [A, C, D, E, Fc] as one value per row.  Diagonal dominance is NOT
+    a condition: the overflow flag and the residual are the safety net."""
+    return eligible_for('cfourier', dict(zip('ACDEF', (A, C, D, E, Fc))), B, Gv, Sv, BCs, undef)
 
 
 def eligible(A, B, C, Fv, Sv, BCs, undef):
-    """The conditions of the Fourier path on the host arrays of one call, in the order of DESIGN.md 4.16; the first that
-    fails raises an Exception naming it.  A, B, C: (array, rowconst) as core._prep_coef returns them (B: None = identically
-    zero); Fv, Sv [nbatch, yc, xc].  -> (A, C) as one value per row."""
-    if B[0] is not None and np.any(np.asarray(B[0]) != 0):
-        _refuse('B must be identically zero (the array B is not)')
-    BCs = list(BCs)
-    if BCs[0] != 'fixed':
-        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along y is %r)" % (BCs[0],))
-    if BCs[1] != 'periodic':
-        _refuse("BCs must be ['fixed', 'periodic'] (the boundary code along x is %r)" % (BCs[1],))
-    Ar, Cr = _per_row('A', *A), _per_row('C', *C)
-    for name, pts, rows in (('F', Fv[:, 1:-1], '1 .. yc-2'), ('A', Ar[..., 1:], '1 .. yc-1'), ('C', Cr[..., 1:-1], '1 .. yc-2'),
-                            ('S', Sv[:, [0, -1]], '0 and yc-1')):
-        if (pts == undef).any():
-            _refuse('no undefined value may sit at a point the solve reads (the array %s holds one on rows %s)' % (name, rows))
-    yc, xc = Fv.shape[-2:]
-    if yc < 3:
-        _refuse('yc must be at least 3, got %d' % yc)
-    err = length_error(xc) if xc >= 3 else 'xc must be at least 3, got %d' % xc
-    if err:
-        _refuse(err)
-    return Ar, Cr
+    """`eligible_for` the 2-D standard form ('fourier') -> (A, C) as one value per row."""
+    return tuple(eligible_for('fourier', dict(A=A, C=C), B, Fv, Sv, BCs, undef))
