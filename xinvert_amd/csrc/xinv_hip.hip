@@ -31,6 +31,7 @@
 #include <thread>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/xinv.h"

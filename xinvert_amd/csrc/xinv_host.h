@@ -391,8 +391,7 @@ static int ensure_pinned(T **p, size_t *cap, size_t need_bytes, unsigned flags)
 }
 
 // ------------------------------------------------------------------ problem description
-enum { KIND_STD2D = 0, KIND_GEN2D = 1, KIND_STD3D = 2, KIND_BIH2D = 3, KIND_STD2DT = 4, KIND_GEN3D = 5 };
-// What the C-ABI's problem builder and validate() need to know about a form, indexed by kind: its coefficient arrays
+// (KIND_*: xinv_dispatch.h)  What the C-ABI's problem builder and validate() need to know about a form, indexed by kind: its coefficient arrays
 // (forcing last), its core rank, whether array 1 (B) may be NULL (identically 0), and the reference's norm == 0 stop
 // (numbas.py:410: the standard 2-D forms only).
 struct FormInfo { int ncoef, rank, null_B, stop_on_zero_norm; };

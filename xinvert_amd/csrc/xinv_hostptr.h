@@ -658,10 +658,10 @@ static int roll_launch(HostCall &h, Roll &R, int l, int64_t i)
         while (f < hi && i - R.join[(size_t)f] == R.L - 1) f++;
         const double *src = R.buf[i & 1]; double *dst = R.buf[(i + 1) & 1];
         if (R.klast == R.Kf) {                       // (a budget that is whole passes: one launch for everybody)
-            r = launch_planned(h.d, R.pl, h.ws, ln.s, R.Kf, src, dst, lo, hi - lo, 0, 0); if (r) return r; R.nlaunch++;
+            r = launch_planned(h.d, R.pl, h.ws, ln.s, SweepLaunch{R.Kf, src, dst, lo, hi - lo}); if (r) return r; R.nlaunch++;
         } else {
-            if (f > lo) { r = launch_planned(h.d, R.pl, h.ws, ln.s, R.klast, src, dst, lo, f - lo, 0, 0); if (r) return r; R.nlaunch++; }
-            if (hi > f) { r = launch_planned(h.d, R.pl, h.ws, ln.s, R.Kf, src, dst, f, hi - f, 0, 0); if (r) return r; R.nlaunch++; }
+            if (f > lo) { r = launch_planned(h.d, R.pl, h.ws, ln.s, SweepLaunch{R.klast, src, dst, lo, f - lo}); if (r) return r; R.nlaunch++; }
+            if (hi > f) { r = launch_planned(h.d, R.pl, h.ws, ln.s, SweepLaunch{R.Kf, src, dst, f, hi - f}); if (r) return r; R.nlaunch++; }
         }
         if (f > lo) {
             HIPCHK(hipMemcpyAsync(R.hc + lo, h.ws->ctl + lo, (size_t)(f - lo) * sizeof(XinvCtl), hipMemcpyDeviceToHost, ln.s));
@@ -694,8 +694,11 @@ static int roll_finish(HostCall &h, Roll &R, const Retired &g)
         const int64_t sw = c.sweeps, rl = (sw - 1) / R.Kf;
         const int src = xinv_pingpong_src(R.join[(size_t)m], rl);
         const XinvFinal w = xinv_final_in(rl * R.Kf, std::min<int64_t>((rl + 1) * R.Kf, R.max_sweeps), src, src ^ 1, 2, false, sw);
-        for (int64_t q = 0; q < w.redo; q++)         // stopped inside a pass: redo from its source, sweep by sweep
-            if ((r = launch_planned(h.d, R.pl, h.ws, g.s, 1, R.buf[xinv_redo_read(w.r, q)], R.buf[xinv_redo_write(w.r, q)], m, 1, 1, 1))) return r;
+        for (int64_t q = 0; q < w.redo; q++) {       // stopped inside a pass: redo from its source, sweep by sweep
+            SweepLaunch one{1, R.buf[xinv_redo_read(w.r, q)], R.buf[xinv_redo_write(w.r, q)], m, 1};
+            one.force = one.no_ctl = 1;
+            if ((r = launch_planned(h.d, R.pl, h.ws, g.s, one))) return r;
+        }
         if (w.where != 0)
             HIPCHK(hipMemcpyAsync(h.d.S + m * h.n, h.ws->S2 + m * h.n, (size_t)h.n * sizeof(double), hipMemcpyDeviceToDevice, g.s));
         member_flags(c, h.flags + 3 * m);

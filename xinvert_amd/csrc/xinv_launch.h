@@ -1,6 +1,6 @@
 // xinv_launch.h -- how a solve is laid out on the GPU: the plan (path, colours, tiling, x-uniform
-// streams, masked-tile skipping), the template dispatch of the fused kernels, the colour-pass
-// launches and the once-per-solve detection passes.  Included by xinv_hip.hip only.
+// streams, masked-tile skipping, the kernel of every pass length), the one launch and occupancy query of the sweep
+// kernels (xinv_dispatch.h), the colour-pass launches and the once-per-solve detection passes.  Included by xinv_hip.hip only.
 #pragma once
 
 // ------------------------------------------------------------------ launch helpers
@@ -45,6 +45,8 @@ struct Plan {
     bool pq;                 // general form with A, C varying along x: the point-factor stream Q (FusedGen2DQ: relaxation
                              // factor and update predicate of every point, evaluated once per coefficient stack);
                              // Q lives in ws->d_pfac (a plan's own buffer while it solves)
+    KernelRef kern[XINV_KMAX + 1];   // the kernel of a pass of k sweeps, k = 1 .. K: the full pass, the shorter tail, the
+                             // one-sweep redo and recovery (plan_kernels; resident plans copy them: process-lifetime addresses)
 };
 
 // kernel variants instantiated per model: mask of streams read as one scalar per row
@@ -70,12 +72,13 @@ static const StreamMap &stream_map(int kind)
     return kind == KIND_STD2D ? std2d : (kind == KIND_STD2DT ? std2dt : gen2d);
 }
 
-// edge strips whose row blocks are cut in two for a tiling of `nstrip` strips (one strip spans the row: it is both)
-// columns a tile owns: 128 minus the 2K halo columns a side (the wave-pipelined pass has K = 4); the odd-xc periodic
-// seam variants own one pair less (k_fused2d: SEAM)
-static inline int strip_uw(const Plan &pl, int K, bool pipe)
+// Columns a tile of this plan owns at K sweeps per pass (`pipe`: of the wave-pipelined pass, which has K = XINV_PIPE_P).
+// 5-point kernels: 128 minus the 2K halo columns a side; 9-point kernel: one halo column per colour and sweep; the
+// odd-xc periodic seam variants own one pair less (the ring layout's strips, xinv_tiles.h); biharmonic kernel: fixed.
+static inline int own_cols(const Problem &p, const Plan &pl, int K, bool pipe = false)
 {
-    // (odd-xc periodic seam: the ring layout's strips, xinv_tiles.h)
+    if (p.kind == KIND_BIH2D) return XINV_BIH_OWN(p.BCx == XINV_BC_PERIODIC);
+    if (pl.nine) return pl.seam ? xinv_ring_uw(pl.xc, 4 * K) : 128 - 8 * K;
     if (pl.seam) return xinv_ring_uw(pl.xc, pipe ? 2 * XINV_PIPE_P : 2 * K);
     return pipe ? XINV_PIPE_UW : 128 - 4 * K;
 }
@@ -97,23 +100,94 @@ static int p3_extend_joff(int64_t yc)
     return xinv_p3_extend_joff(yc, XINV_P3_G * XINV_P3_RR - 8, 4, XINV_P3_RR);
 }
 
-static int fused_dispatch(int kind, bool al, bool ext, unsigned um, int K, dim3 grid, dim3 block,
-                          hipStream_t st, const FusedArgs &a, int *occ, bool seam = false, bool fma = false, bool pq = false)
+// ------------------------------------------------------------------ the sweep kernels: variant -> kernel, launch, occupancy
+// The unit that holds a variant (xinv_dispatch.h); fn == nullptr where none does.
+static KernelRef xinv_kernel(const SweepVariant &v)
 {
-    if (pq) return (kind != KIND_GEN2D || seam || fma) ? 1 : xinv_launch_fused2d_genq(al, ext, um, K, grid, block, st, a, occ);   // (um | 2: the A == C variant)
-    if (fma) {                                           // contracted arithmetic (xinv_fused.h: FusedStd2DF / FusedGen2DF)
-        if (seam || kind == KIND_STD2DT) return 1;
-        return kind == KIND_GEN2D ? xinv_launch_fused2d_genf(al, ext, um, K, grid, block, st, a, occ)
-                                  : xinv_launch_fused2d_stdf(al, ext, um, K, grid, block, st, a, occ);
+    const bool gen = v.kind == KIND_GEN2D, test = v.kind == KIND_STD2DT;
+    switch (v.family) {
+    case FAM_FUSED2D:
+        if (v.pq) return (!gen || v.seam || v.fma) ? KernelRef{} : xinv_kernel_fused2d<FUSED2D_GENQ, false>(v);
+        if (v.fma) {                                     // contracted arithmetic (xinv_fused.h: FusedStd2DF / FusedGen2DF)
+            if (v.seam || test) return KernelRef{};
+            return gen ? xinv_kernel_fused2d<FUSED2D_GENF, false>(v) : xinv_kernel_fused2d<FUSED2D_STDF, false>(v);
+        }
+        if (v.seam)                                      // odd-xc periodic seam variants (xinv_fused.h: SEAM)
+            return gen ? xinv_kernel_fused2d<FUSED2D_GEN, true>(v)
+                       : (test ? xinv_kernel_fused2d<FUSED2D_STD2DT, true>(v) : xinv_kernel_fused2d<FUSED2D_STD, true>(v));
+        return gen ? xinv_kernel_fused2d<FUSED2D_GEN, false>(v)
+                   : (test ? xinv_kernel_fused2d<FUSED2D_STD2DT, false>(v) : xinv_kernel_fused2d<FUSED2D_STD, false>(v));
+    case FAM_PIPE2D:
+        if (v.fma) return v.seam ? KernelRef{} : xinv_kernel_pipe2d<PIPE2D_FMA, false>(v);
+        if (v.seam) return gen ? xinv_kernel_pipe2d<PIPE2D_GEN, true>(v) : xinv_kernel_pipe2d<PIPE2D_STD, true>(v);
+        return gen ? xinv_kernel_pipe2d<PIPE2D_GEN, false>(v) : xinv_kernel_pipe2d<PIPE2D_STD, false>(v);
+    case FAM_FUSED9: return xinv_kernel_fused9(v);
+    case FAM_FUSED3D: return v.seam ? xinv_kernel_fused3d_seam(v) : (v.fma ? xinv_kernel_fused3d_fma(v) : xinv_kernel_fused3d(v));
+    case FAM_FUSED3DG: return v.seam ? xinv_kernel_fused3d_seam(v) : xinv_kernel_fused3d(v);
+    case FAM_PIPE3D: return xinv_kernel_pipe3d(v);
+    case FAM_BIH: return xinv_kernel_bih(v);
     }
-    if (seam) {                                          // odd-xc periodic seam variants (xinv_fused.h: SEAM)
-        if (kind == KIND_GEN2D) return xinv_launch_fused2d_gen_seam(al, ext, um, K, grid, block, st, a, occ);
-        if (kind == KIND_STD2DT) return xinv_launch_fused2d_std2dt_seam(al, ext, um, K, grid, block, st, a, occ);
-        return xinv_launch_fused2d_std_seam(al, ext, um, K, grid, block, st, a, occ);
+    return KernelRef{};
+}
+
+// `args`: the kernel's one argument struct (FusedArgs, Fused3Args, Fused3GArgs, FusedBihArgs -- what its family takes)
+template <class A>
+static inline void kernel_launch(KernelRef k, dim3 grid, size_t lds, hipStream_t st, const A &args)
+{
+    void *argv[1] = {const_cast<A *>(&args)};
+    (void)hipLaunchKernel(k.fn, grid, dim3(k.threads, 1, 1), argv, lds, st);     // (errors: the caller's hipGetLastError)
+}
+
+// Workgroups of a kernel that fit on a CU (register-limited), 1 where the runtime cannot say.  Asked of the runtime once
+// per kernel and process (the planner asks in every solve: a few microseconds per query); several planner threads may ask.
+static int kernel_occupancy(KernelRef k)
+{
+    static std::mutex mu;
+    static std::unordered_map<const void *, int> known;
+    std::lock_guard<std::mutex> lock(mu);
+    int &n = known[k.fn];
+    if (!n && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.fn, (int)k.threads, 0) != hipSuccess || n < 1)) n = 1;
+    return n;
+}
+
+// One sweep launch of a plan: k sweeps from src into dst (fused path; the colour path sweeps p.S in place) for members
+// [member0, member0 + nmem).  force: also members that have stopped; no_ctl: no norm, no stop rule.
+// Lagged norm (run_sweeps): the launch publishes with `lag_tag` into the partial buffer of its parity; its extra
+// workgroup evaluates `lag_prev`; `lag_out` receives what the evaluation of THIS launch needs.
+// prepass = false (biharmonic form, 'extend'): the source already carries this pass's pre-pass (launch_fusedbih).
+struct SweepLaunch {
+    int k;
+    const double *src;
+    double *dst;
+    int64_t member0, nmem;
+    int force = 0, no_ctl = 0;
+    unsigned lag_tag = 0;
+    NormLagArgs *lag_out = nullptr;
+    const NormLagArgs *lag_prev = nullptr;
+    bool prepass = true;
+};
+
+// The instantiation a pass of k sweeps of this plan runs: the wave-pipelined kernels for the full pass of a pipelined
+// plan (2-D: k == pl.K; standard 3-D form: k == 2), the one-tile-per-wavefront kernels for every shorter one.
+static SweepVariant plan_variant(const Problem &p, const Plan &pl, int k)
+{
+    SweepVariant v;
+    memset(&v, 0, sizeof v);
+    v.kind = p.kind; v.K = k;
+    v.al = pl.aligned; v.ext = (p.BCy == XINV_BC_EXTEND); v.seam = pl.seam != 0; v.fma = pl.fma;
+    if (p.kind == KIND_BIH2D) {
+        v.family = FAM_BIH; v.per = (p.BCx == XINV_BC_PERIODIC); v.zbe = pl.bih_zbe; v.vm = pl.bih_vm;
+    } else if (is3d(p.kind)) {
+        v.family = p.kind == KIND_GEN3D ? FAM_FUSED3DG : (k == 2 ? FAM_PIPE3D : FAM_FUSED3D);
+        v.NW = pl.RY; v.uni = (pl.um == 7u);
+    } else if (pl.nine) {
+        v.family = FAM_FUSED9;
+    } else if (pl.pipe && k == pl.K) {
+        v.family = FAM_PIPE2D; v.um = pl.um; v.pipe_fr = pl.pipe_fr;
+    } else {
+        v.family = FAM_FUSED2D; v.um = pl.um | (pl.alias_ac ? 2u : 0u); v.pq = pl.pq;      // (um | 2: the A == C variant)
     }
-    if (kind == KIND_GEN2D) return xinv_launch_fused2d_gen(al, ext, um, K, grid, block, st, a, occ);
-    if (kind == KIND_STD2DT) return xinv_launch_fused2d_std2dt(al, ext, um, K, grid, block, st, a, occ);
-    return xinv_launch_fused2d_std(al, ext, um, K, grid, block, st, a, occ);
+    return v;
 }
 
 static bool ptr_al16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
@@ -177,35 +251,32 @@ static void set_skip(A &a, const Workspace *ws, const Problem &p, const Plan &pl
     a.xsum = t.xsum; a.xcnt = t.xcnt;
 }
 
-// Lagged norm (run_sweeps): this launch publishes with `lag_tag` into the partial buffer of its parity;
-// its extra workgroup evaluates `lag_prev`; `lag_out` receives what the evaluation of THIS launch needs.
-// `a` is a FusedArgs / FusedBihArgs whose psum / xsum / xcnt / nwg are already final.
+// The lagged norm of launch L (SweepLaunch): `a` is a FusedArgs / FusedBihArgs whose psum / xsum / xcnt / nwg are
+// already final, K the sweeps of the pass.
 template <class A>
-static void set_lag(A &a, const Workspace *ws, const Problem &p, int K, unsigned lag_tag, NormLagArgs *lag_out,
-                    const NormLagArgs *lag_prev)
+static void set_lag(A &a, const Workspace *ws, const Problem &p, int K, const SweepLaunch &L)
 {
-    if (lag_tag) {
-        a.lag = 1; a.tag = lag_tag;
-        a.psum = (unsigned long long *)((char *)ws->partials + (size_t)((lag_tag - 1u) & 1u) * ws->partials_half);
-        if (lag_prev && lag_prev->tag) {
-            a.lagp_psum = lag_prev->psum; a.lagp_xsum = lag_prev->xsum; a.lagp_xcnt = lag_prev->xcnt;
-            a.lagp_NB = lag_prev->NB; a.lagp_K = lag_prev->K; a.lagp_tag = lag_prev->tag;
+    if (L.lag_tag) {
+        a.lag = 1; a.tag = L.lag_tag;
+        a.psum = (unsigned long long *)((char *)ws->partials + (size_t)((L.lag_tag - 1u) & 1u) * ws->partials_half);
+        if (L.lag_prev && L.lag_prev->tag) {
+            a.lagp_psum = L.lag_prev->psum; a.lagp_xsum = L.lag_prev->xsum; a.lagp_xcnt = L.lag_prev->xcnt;
+            a.lagp_NB = L.lag_prev->NB; a.lagp_K = L.lag_prev->K; a.lagp_tag = L.lag_prev->tag;
         }
     }
-    if (lag_out) {
-        memset(lag_out, 0, sizeof *lag_out);
-        lag_out->psum = a.psum; lag_out->ctl = ws->ctl; lag_out->stop = p.stop;
-        lag_out->xsum = a.xsum; lag_out->xcnt = a.xcnt; lag_out->NB = a.nwg; lag_out->K = K; lag_out->tag = lag_tag;
+    if (L.lag_out) {
+        memset(L.lag_out, 0, sizeof *L.lag_out);
+        L.lag_out->psum = a.psum; L.lag_out->ctl = ws->ctl; L.lag_out->stop = p.stop;
+        L.lag_out->xsum = a.xsum; L.lag_out->xcnt = a.xcnt; L.lag_out->NB = a.nwg; L.lag_out->K = K; L.lag_out->tag = L.lag_tag;
     }
 }
 
 // What the 5-point and the 9-point launch fill alike: everything of FusedArgs but the coefficient streams, for strips of
 // UW owned columns and four wave-tiles per workgroup.
-static void fused_args(FusedArgs &a, const Problem &p, const Plan &pl, const Workspace *ws, const double *src, double *dst,
-                       int UW, int force, int no_ctl)
+static void fused_args(FusedArgs &a, const Problem &p, const Plan &pl, const Workspace *ws, const SweepLaunch &L, int UW)
 {
     memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst; a.sS = p.sS;
+    a.src = L.src; a.dst = L.dst; a.sS = p.sS;
     a.yc = p.yc; a.xc = p.xc;
     a.per = (p.BCx == XINV_BC_PERIODIC);
     a.ext = (p.BCy == XINV_BC_EXTEND);
@@ -214,19 +285,17 @@ static void fused_args(FusedArgs &a, const Problem &p, const Plan &pl, const Wor
     a.nstrip = (int)cdiv(p.xc, UW);
     a.nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
     a.nwg = (int)cdiv((int64_t)a.nstrip * a.nrb, 4);
-    a.force = force; a.no_ctl = no_ctl;
+    a.force = L.force; a.no_ctl = L.no_ctl;
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     a.psum = (unsigned long long *)ws->partials;
 }
 
-static int launch_fused(const Problem &p, const Plan &pl, int K, const double *src, double *dst,
-                        Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
-                        int no_ctl, unsigned lag_tag = 0, NormLagArgs *lag_out = nullptr,
-                        const NormLagArgs *lag_prev = nullptr)
+static int launch_fused(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, const SweepLaunch &L)
 {
     FusedArgs a;
+    const int K = L.k;
     const bool pipe = pl.pipe && K == pl.K;          // wave-pipelined pass: one tile per workgroup
-    fused_args(a, p, pl, ws, src, dst, strip_uw(pl, K, pipe), force, no_ctl);
+    fused_args(a, p, pl, ws, L, own_cols(p, pl, K, pipe));
     const StreamMap &sm = stream_map(p.kind);
     for (int q = 0; q < sm.n; q++) { a.c[q] = p.c[sm.c[q]]; a.sc[q] = p.sc[sm.c[q]]; }
     if (pl.pq) {                                     // A, C, D, E, F, Q, G (FusedGen2DQ): Q in front of the forcing
@@ -241,22 +310,15 @@ static int launch_fused(const Problem &p, const Plan &pl, int K, const double *s
     a.dbg = (double *)t_hook_record;                 // (run_sweeps: XINV_HOOK_SKIP_PUBLISH; nullptr otherwise)
 #endif
     if (pl.skip && K == pl.K) set_skip(a, ws, p, pl, pl.tpw);       // the lists were built for this K's strips
-    set_lag(a, ws, p, K, lag_tag, lag_out, lag_prev);
-    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+    set_lag(a, ws, p, K, L);
+    for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
         a.member0 = m;
-        dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1), block(256, 1, 1);
-        if (pipe) {
-            // (XINV_PIPE_LDSPAD: unused dynamic LDS per workgroup, to cap the workgroups per CU in experiments;
-            //  capping at the planned count changed nothing: the dispatcher already spreads them evenly)
-            const int pad = std::max(0, XINV_ENV_INT("XINV_PIPE_LDSPAD", 0));
-            xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.pipe_fr, pl.aligned, a.ext != 0, grid, st, a, nullptr, pad, pl.seam != 0, pl.fma);
-            return XINV_OK;
-        }
-        if (fused_dispatch(p.kind, pl.aligned, a.ext != 0, pl.um | (pl.alias_ac ? 2u : 0u), K, grid, block, st, a, nullptr, pl.seam != 0, pl.fma, pl.pq))
-            return fail_arg("unsupported sweeps_per_launch for this kernel variant");
+        dim3 grid((unsigned)a.nwg + (L.lag_tag ? 1u : 0u), (unsigned)nm, 1);
+        // (XINV_PIPE_LDSPAD: unused dynamic LDS per workgroup of the pipelined pass, to cap the workgroups per CU in
+        //  experiments; capping at the planned count changed nothing: the dispatcher already spreads them evenly)
+        kernel_launch(pl.kern[K], grid, pipe ? (size_t)std::max(0, XINV_ENV_INT("XINV_PIPE_LDSPAD", 0)) : 0, st, a);
         return XINV_OK;
     });
-    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -274,7 +336,7 @@ static int launch_pipe_masks(const Problem &p, const Plan &pl, Workspace *ws, hi
     ma.rowf = (const double *)ws->d_rowf; ma.rw = pipe_rec_shape(p.kind).rw; ma.irok = pipe_rec_shape(p.kind).irok;
     ma.yc = p.yc; ma.xc = p.xc;
     ma.per = (p.BCx == XINV_BC_PERIODIC); ma.al = pl.aligned; ma.seam = pl.seam != 0;
-    ma.nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    ma.nstrip = (int)cdiv(p.xc, own_cols(p, pl, pl.K, true));
     ma.undef = p.sc_.undef; ma.mask = ws->d_pmask;
     const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
         ma.member0 = m;
@@ -286,48 +348,35 @@ static int launch_pipe_masks(const Problem &p, const Plan &pl, Workspace *ws, hi
     return XINV_OK;
 }
 
-// columns a wavefront of the 9-point kernel owns (one halo column per colour and sweep; the seam variants one pair less)
-static inline int strip9_uw(const Plan &pl, int K) { return pl.seam ? xinv_ring_uw(pl.xc, 4 * K) : 128 - 8 * K; }   // (seam: the ring layout, xinv_tiles.h)
-
-static int launch_fused9(const Problem &p, const Plan &pl, int K, const double *src, double *dst,
-                         Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
-                         int no_ctl, unsigned lag_tag = 0, NormLagArgs *lag_out = nullptr,
-                         const NormLagArgs *lag_prev = nullptr)
+static int launch_fused9(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, const SweepLaunch &L)
 {
     FusedArgs a;
-    fused_args(a, p, pl, ws, src, dst, strip9_uw(pl, K), force, no_ctl);
+    fused_args(a, p, pl, ws, L, own_cols(p, pl, L.k));
     const int nc = (p.kind == KIND_GEN2D) ? 7 : 4;
     for (int q = 0; q < nc; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
-    if (pl.skip && K == pl.K) set_skip(a, ws, p, pl, 4);
-    set_lag(a, ws, p, K, lag_tag, lag_out, lag_prev);
-    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+    if (pl.skip && L.k == pl.K) set_skip(a, ws, p, pl, 4);
+    set_lag(a, ws, p, L.k, L);
+    for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
         a.member0 = m;
-        dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1);
-        if (xinv_launch_fused9(p.kind == KIND_GEN2D, K, pl.aligned, a.ext != 0, grid, st, a, nullptr, pl.seam != 0))
-            return fail_arg("unsupported sweeps_per_launch for the 9-point kernel");
+        kernel_launch(pl.kern[L.k], dim3((unsigned)a.nwg + (L.lag_tag ? 1u : 0u), (unsigned)nm, 1), 0, st, a);
         return XINV_OK;
     });
-    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
 
-static int launch_fused3d(const Problem &p, const Plan &pl, int K, const double *src, double *dst,
-                          Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
-                          int no_ctl)
+static int launch_fused3d(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, const SweepLaunch &L)
 {
     Fused3Args a;
     memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst; a.sS = p.sS;
+    a.src = L.src; a.dst = L.dst; a.sS = p.sS;
     for (int q = 0; q < 4; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
     a.zc = p.zc; a.yc = p.yc; a.xc = p.xc;
     a.per = (p.BCx == XINV_BC_PERIODIC);
-    a.force = force; a.no_ctl = no_ctl;
+    a.force = L.force; a.no_ctl = L.no_ctl;
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     a.psum = (unsigned long long *)ws->partials;
-    int rc;
-    if (K == 2) {                                        // two sweeps per pass: its own tiling
-        if (!pl.K2) return fail_arg("internal: two-sweep 3-D pass without its plan");
+    if (L.k == 2) {                                      // two sweeps per pass (k_pipe3d): its own tiling
         a.nstrip = pl.nsg2; a.njb = pl.nrb2; a.joff = pl.joff2;
         a.nkc = std::max(1, pl.nkc2); a.KC = pl.KC2;
         a.rowf = (const double *)ws->d_rowf; a.srowf = pl.srowf2;
@@ -335,100 +384,82 @@ static int launch_fused3d(const Problem &p, const Plan &pl, int K, const double 
         // a flat grid over the members of the launch (k_pipe3d); at most 2^30 workgroups per launch
         const int64_t mstep = std::max<int64_t>(1, std::min<int64_t>(XINV_MEMBER_CHUNK, ((int64_t)1 << 30) / (NT2 * a.nkc)));
         const bool ext2 = (p.BCy == XINV_BC_EXTEND);
-        rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
             a.member0 = m;
             // 'extend': the pre-pass of the pass's first sweep, in place on the source (numbas.py:87-115; idempotent: a
             // pass redone from this source by the one-sweep kernel applies it again to the same effect); the second
             // sweep's is applied inside the kernel (xinv_pipe3d.h: EXT).  A no-op for a member that has stopped.
             if (ext2)
-                for_member_chunks(m, nm, [&](int64_t q, int64_t nq) { launch_extend(p, ws, st, const_cast<double *>(src), force, q, nq); return XINV_OK; });
+                for_member_chunks(m, nm, [&](int64_t q, int64_t nq) { launch_extend(p, ws, st, const_cast<double *>(L.src), L.force, q, nq); return XINV_OK; });
             // which tiles march the whole column, which are cut into the plan's k chunks (xinv_p3_whole_tiles)
             a.nfull = xinv_p3_whole_tiles(NT2 * nm, a.nkc, a.KC, p.zc, pl.cus);
             const int64_t nwg = a.nfull + (NT2 * nm - a.nfull) * a.nkc;
-            if (pl.fma) xinv_launch_pipe3d_fma(pl.aligned, dim3((unsigned)nwg, 1, 1), st, a);
-            else        xinv_launch_pipe3d(pl.aligned, dim3((unsigned)nwg, 1, 1), st, a, pl.seam != 0, ext2);
+            kernel_launch(pl.kern[2], dim3((unsigned)nwg, 1, 1), 0, st, a);
             return XINV_OK;
         }, mstep);
     } else {
         a.nstrip = pl.nsg; a.njb = pl.nrb;
         a.nkc = std::max(1, pl.nkc); a.KC = pl.KC;
         const size_t NB = (size_t)pl.nsg * pl.nrb * a.nkc;
-        const bool ext = (p.BCy == XINV_BC_EXTEND), uni = (pl.um == 7u);
-        rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+        for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
             a.member0 = m;
-            dim3 grid((unsigned)NB, (unsigned)nm, 1);
-            if (pl.seam ? xinv_launch_fused3d_seam(pl.RY, uni, ext, grid, st, a)
-                : pl.fma ? xinv_launch_fused3d_fma(pl.RY, pl.aligned, ext, grid, st, a)
-                         : xinv_launch_fused3d(pl.RY, pl.aligned, uni, ext, grid, st, a))
-                return fail_arg("internal: no 3-D kernel variant for this cross-section");
+            kernel_launch(pl.kern[L.k], dim3((unsigned)NB, (unsigned)nm, 1), 0, st, a);
             return XINV_OK;
         });
     }
-    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
 
 // ---- biharmonic one-pass launch (A..I x-uniform) ----------------------------------------------
-static int launch_fusedbih(const Problem &p, const Plan &pl, const double *src, double *dst,
-                           Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
-                           int no_ctl, unsigned lag_tag = 0, NormLagArgs *lag_out = nullptr,
-                           const NormLagArgs *lag_prev = nullptr, bool prepass = true)
+static int launch_fusedbih(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, const SweepLaunch &L)
 {
-    const bool per = (p.BCx == XINV_BC_PERIODIC);
     // (prepass = false: finalise() redoing a pass whose source already carries that pass's pre-pass -- the periodic
     //  pre-pass, r0 <- r1 then r1 <- r2, is not idempotent)
-    if (p.BCy == XINV_BC_EXTEND && prepass)          // the kernel's own pre-pass, on the source buffer
-        for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) { launch_extend(p, ws, st, const_cast<double *>(src), force, m, nm); return XINV_OK; });
+    if (p.BCy == XINV_BC_EXTEND && L.prepass)        // the kernel's own pre-pass, on the source buffer
+        for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) { launch_extend(p, ws, st, const_cast<double *>(L.src), L.force, m, nm); return XINV_OK; });
     FusedBihArgs a;
     memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst; a.sS = p.sS;
+    a.src = L.src; a.dst = L.dst; a.sS = p.sS;
     for (int q = 0; q < 10; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
-    a.yc = p.yc; a.xc = p.xc; a.per = per;
-    a.nstrip = (int)cdiv(p.xc, XINV_BIH_OWN(per)); a.nrb = pl.nrb; a.RB = pl.RY;
+    a.yc = p.yc; a.xc = p.xc; a.per = (p.BCx == XINV_BC_PERIODIC);
+    a.nstrip = (int)cdiv(p.xc, own_cols(p, pl, 1)); a.nrb = pl.nrb; a.RB = pl.RY;
     a.nwg = (int)cdiv((int64_t)a.nstrip * a.nrb, 4);
-    a.force = force; a.no_ctl = no_ctl;
+    a.force = L.force; a.no_ctl = L.no_ctl;
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     a.rowf = (const double *)ws->d_rowf;
     a.q = pl.bih_vm ? (const double *)ws->d_pfac : nullptr;
     a.psum = (unsigned long long *)ws->partials;
     if (pl.skip) set_skip(a, ws, p, pl, 4);
-    set_lag(a, ws, p, 1, lag_tag, lag_out, lag_prev);
-    for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+    set_lag(a, ws, p, 1, L);
+    for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
         a.member0 = m;
-        dim3 grid((unsigned)a.nwg + (lag_tag ? 1u : 0u), (unsigned)nm, 1);
-        xinv_launch_fusedbih(per, pl.bih_zbe, pl.bih_vm, grid, st, a, nullptr);
+        kernel_launch(pl.kern[1], dim3((unsigned)a.nwg + (L.lag_tag ? 1u : 0u), (unsigned)nm, 1), 0, st, a);
         return XINV_OK;
     });
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
 
-static int launch_fused3dg(const Problem &p, const Plan &pl, const double *src, double *dst,
-                           Workspace *ws, hipStream_t st, int64_t member0, int64_t nmem, int force,
-                           int no_ctl)
+static int launch_fused3dg(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t st, const SweepLaunch &L)
 {
     Fused3GArgs a;
     memset(&a, 0, sizeof a);
-    a.src = src; a.dst = dst; a.sS = p.sS;
+    a.src = L.src; a.dst = L.dst; a.sS = p.sS;
     for (int q = 0; q < 8; q++) { a.c[q] = p.c[q]; a.sc[q] = p.sc[q]; }
     a.zc = p.zc; a.yc = p.yc; a.xc = p.xc;
     a.per = (p.BCx == XINV_BC_PERIODIC);
     a.nstrip = pl.nsg; a.njb = pl.nrb;
     a.nkc = std::max(1, pl.nkc); a.KC = pl.KC;
-    a.force = force; a.no_ctl = no_ctl;
+    a.force = L.force; a.no_ctl = L.no_ctl;
     a.sc_ = p.sc_; a.ctl = ws->ctl; a.stop = p.stop;
     const size_t NB = (size_t)pl.nsg * pl.nrb * a.nkc;
     a.psum = (unsigned long long *)ws->partials;
-    const bool ext = (p.BCy == XINV_BC_EXTEND);
-    const int rc = for_member_chunks(member0, nmem, [&](int64_t m, int64_t nm) {
+    for_member_chunks(L.member0, L.nmem, [&](int64_t m, int64_t nm) {
         a.member0 = m;
-        dim3 grid((unsigned)NB, (unsigned)nm, 1);
-        if (pl.seam ? xinv_launch_fused3dg_seam(pl.RY, ext, grid, st, a) : xinv_launch_fused3dg(pl.RY, pl.aligned, ext, grid, st, a))
-            return fail_arg("internal: no general 3-D kernel variant for this cross-section");
+        kernel_launch(pl.kern[1], dim3((unsigned)NB, (unsigned)nm, 1), 0, st, a);
         return XINV_OK;
     });
-    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return XINV_OK;
 }
@@ -562,26 +593,17 @@ static int64_t choose_row_blocks(int64_t yc, int64_t nstrip, int64_t nbatch, int
                                   pipe ? XINV_PIPE_B : 0, XINV_PIPE_PF0 + 4, XINV_PIPE_PF + 4);
 }
 
-// How many workgroups of the planned kernel variant fit on a CU at K sweeps per pass (register-limited: asked of the
-// runtime through the family's launcher, with zeroed arguments and `occ` set).  *have (when given): the variant exists;
-// where it does not, the answer is the family's default.
-static int plan_occ(const Problem &p, const Plan &pl, hipStream_t st, int K, bool *have = nullptr)
+// How many workgroups of the planned kernel variant fit on a CU at K sweeps per pass (2-D forms; the 3-D kernels fill a
+// CU with one).  *have (when given): the variant exists; where it does not, the answer is the family's default.
+static int plan_occ(const Problem &p, const Plan &pl, int K, bool *have = nullptr)
 {
-    const bool ext = (p.BCy == XINV_BC_EXTEND);
-    int occ, missing;
-    if (p.kind == KIND_BIH2D) {
-        FusedBihArgs dummy; memset(&dummy, 0, sizeof dummy);
-        occ = 1;
-        missing = xinv_launch_fusedbih(false, pl.bih_zbe, pl.bih_vm, dim3(1), st, dummy, &occ);
-    } else {
-        FusedArgs dummy; memset(&dummy, 0, sizeof dummy);
-        occ = pl.nine ? 1 : 2;
-        if (pl.nine) missing = xinv_launch_fused9(p.kind == KIND_GEN2D, K, pl.aligned, ext, dim3(1), st, dummy, &occ, pl.seam != 0);
-        else if (pl.pipe) missing = xinv_launch_pipe2d(p.kind == KIND_GEN2D, pl.um, pl.pipe_fr, pl.aligned, ext, dim3(1), st, dummy, &occ, 0, pl.seam != 0, pl.fma);
-        else missing = fused_dispatch(p.kind, pl.aligned, ext, pl.um | (pl.alias_ac ? 2u : 0u), K, dim3(1), dim3(256), st, dummy, &occ, pl.seam != 0, pl.fma, pl.pq);
-    }
-    if (have) *have = !missing;
-    return occ;
+    SweepVariant v = plan_variant(p, pl, K);
+    // (the biharmonic tiling has always been planned with the non-periodic kernel of the plan's stream mode, with the
+    //  mixed terms unless that mode never has them: a plan's row split must not move with which one is asked)
+    if (p.kind == KIND_BIH2D) v.per = v.zbe = false;
+    const KernelRef k = xinv_kernel(v);
+    if (have) *have = k.fn != nullptr;
+    return k.fn ? kernel_occupancy(k) : (pl.nine ? 1 : 2);
 }
 
 // rows_per_tile > 0: tiles of that many rows (rounded up to even); < 0: exactly that many row blocks, split evenly; 0
@@ -614,7 +636,7 @@ static inline PipeTileGeom pipe_tile_geom()
 static int plan_pipe_tile_recs(const Problem &p, Plan &pl, Workspace *ws, hipStream_t st)
 {
     if (!pl.pipe || pl.skip) return XINV_OK;
-    const int nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    const int nstrip = (int)cdiv(p.xc, own_cols(p, pl, pl.K, true));
     const int RY = pl.even_split ? 0 : pl.RY, nrb = pl.even_split ? pl.nrb : (int)cdiv(p.yc, pl.RY);
     const bool per = p.BCx == XINV_BC_PERIODIC;
     pl.trec_off = 0; pl.trec_ms = 0;
@@ -639,7 +661,7 @@ static int plan_pipe_tile_recs(const Problem &p, Plan &pl, Workspace *ws, hipStr
 // reference tests the forcing), so launches run the other tiles only; the row split is re-chosen
 // so that the ACTIVE tiles fill the CUs evenly, and the skipped tiles' constant share of the norm
 // is computed once.  Decided per solve from one pass over the forcing.
-// `fixedRB` > 0 (biharmonic one-pass kernel): tiles are row blocks of exactly fixedRB rows x `UW_` owned
+// `fixedRB` > 0 (biharmonic one-pass kernel): tiles are row blocks of exactly fixedRB rows x own_cols() owned
 // columns and the split is kept; 0: the 5-point kernels' even split, re-planned for the active tiles.
 // The activity map of the forcing for strips of UW owned columns: kernel + copy to the host, NOT synchronised.  The planner
 // of the lat-lon forms issues it ahead of the x-uniform detection with the strip width those forms end up with, so that
@@ -662,12 +684,12 @@ static int issue_strip_active(const Problem &p, Workspace *ws, hipStream_t st, i
 }
 
 static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t st,
-                          const xinv_options &opt, int fixedRB = 0, int UW_ = 0)
+                          const xinv_options &opt, int fixedRB = 0)
 {
     pl.skip = false; pl.ntl = pl.nskip = 0; pl.skip_pct = 0; pl.skip_ppm = 0;
     const bool forced = (opt.flags & XINV_FLAG_FORCE_TILE_SKIP) != 0;
     const int tpw = pl.pipe ? 1 : 4;                              // wave-tiles per workgroup
-    const int K = pl.K, UW = UW_ ? UW_ : strip_uw(pl, K, pl.pipe);   // 9-point kernel: 128 - 8K owned columns
+    const int K = pl.K, UW = own_cols(p, pl, K, pl.pipe);
     const int nstrip = (int)cdiv(p.xc, UW);
     const int64_t wscale = 4 / tpw;                       // (thresholds in wavefronts: a pipelined tile has four)
     if (!forced && ((int64_t)nstrip * pl.nrb * p.nbatch * wscale < 1024 || (int64_t)nstrip * pl.nrb * wscale < 64 ||
@@ -737,7 +759,7 @@ static int plan_tile_skip(const Problem &p, Plan &pl, Workspace *ws, hipStream_t
         if (maxact) *maxact = mx;
         return wgs;
     };
-    const int occ = fixedRB ? 2 : plan_occ(p, pl, st, K);
+    const int occ = fixedRB ? 2 : plan_occ(p, pl, K);
     const bool pp = pl.pipe;
     // the rows tile_cost is handed for a split into nrb blocks: the pipelined pass is costed by its tallest tile
     auto cost_rows = [&](int nrb) -> int64_t {

@@ -70,7 +70,7 @@ static int plan_fusedbih(const Problem &p, const xinv_options &opt, Workspace *w
 {
     pl.K = 1;
     pl.aligned = false;
-    const int nstrip = (int)cdiv(p.xc, XINV_BIH_OWN(p.BCx == XINV_BC_PERIODIC));
+    const int nstrip = (int)cdiv(p.xc, own_cols(p, pl, pl.K));
     int flag = 0;
     // no mixed derivatives (B == E == 0 everywhere)?  One flag pass over the two arrays.
     int rc = any_nonzero(p, ws, st, {1, 4}, &flag);
@@ -101,7 +101,7 @@ static int plan_fusedbih(const Problem &p, const xinv_options &opt, Workspace *w
             return XINV_OK;
         }
     }
-    const int occ = plan_occ(p, pl, st, pl.K);
+    const int occ = plan_occ(p, pl, pl.K);
     {   // per-row records (A..I, relaxation factor, row predicate), once per solve: xinv_fusedbih.h
         rc = ensure_dev(&ws->d_rowf, &ws->d_rowf_cap, (size_t)p.nbatch * p.yc * XINV_BIH_RW * sizeof(double));
         if (rc) return rc;
@@ -140,7 +140,7 @@ static int plan_fusedbih(const Problem &p, const xinv_options &opt, Workspace *w
     pl.nrb = (int)cdiv(p.yc, bestRB);
     pl.nsg = (int)cdiv((int64_t)nstrip * pl.nrb, 4) + 1;
     if (!(opt.flags & XINV_FLAG_NO_TILE_SKIP)) {
-        rc = plan_tile_skip(p, pl, ws, st, opt, bestRB, XINV_BIH_OWN(p.BCx == XINV_BC_PERIODIC));
+        rc = plan_tile_skip(p, pl, ws, st, opt, bestRB);
         if (rc) return rc;
     }
     return XINV_OK;
@@ -156,16 +156,16 @@ static int plan_fused9(const Problem &p, const xinv_options &opt, Workspace *ws,
     pl.aligned = !(p.xc & 1) && vec_aligned(p.S, p.sS);
     for (int q = 0; q < p.ncoef; q++) pl.aligned = pl.aligned && vec_aligned(p.c[q], p.sc[q]);
     if (!rows_per_tile_given(p, opt, pl)) {
-        const int occ = plan_occ(p, pl, st, pl.K);
+        const int occ = plan_occ(p, pl, pl.K);
         // the 9-point kernels stream every coefficient array and sit at the fabric's bandwidth
         // (6+ TB/s): halo re-reads cost more than occupancy gives, so one workgroup per CU
         // (tall tiles) is the target -- measured +25 % (standard, K=1) / +21 % (general) at 2000x2000
         pl.lone = 1.0;
-        split_rows_evenly(p, pl, choose_row_blocks(p.yc, cdiv(p.xc, strip9_uw(pl, pl.K)), p.nbatch, pl.K, occ, pl.lone, false));
+        split_rows_evenly(p, pl, choose_row_blocks(p.yc, cdiv(p.xc, own_cols(p, pl, pl.K)), p.nbatch, pl.K, occ, pl.lone, false));
     }
-    pl.nsg = (int)cdiv((int64_t)cdiv(p.xc, strip9_uw(pl, XINV_KMAX)) * pl.nrb, 4) + 1;
+    pl.nsg = (int)cdiv((int64_t)cdiv(p.xc, own_cols(p, pl, XINV_KMAX)) * pl.nrb, 4) + 1;
     if (pl.even_split && !(opt.flags & XINV_FLAG_NO_TILE_SKIP))
-        return plan_tile_skip(p, pl, ws, st, opt, 0, strip9_uw(pl, pl.K));
+        return plan_tile_skip(p, pl, ws, st, opt);
     return XINV_OK;
 }
 
@@ -259,7 +259,7 @@ static int plan5_xuniform(const Problem &p, const xinv_options &opt, Workspace *
         if (p.kind != KIND_STD2DT && opt.rows_per_tile == 0 && opt.sweeps_per_launch == 0 &&
             !(opt.flags & (XINV_FLAG_NO_TILE_SKIP | XINV_FLAG_NO_PIPE)) && p.nbatch <= 64 &&
             p.nbatch * p.yc * p.xc >= (int64_t)2000000) {
-            const int uw_pipe = pl.seam ? xinv_ring_uw(p.xc, 2 * XINV_PIPE_P) : XINV_PIPE_UW;
+            const int uw_pipe = own_cols(p, pl, XINV_PIPE_P, true);
             if (p.xc >= uw_pipe && p.nbatch * cdiv(p.xc, uw_pipe) * (p.yc + 1) <= (int64_t)50000000) {
                 const int rc = issue_strip_active(p, ws, st, uw_pipe, sm.c[sm.forcing]);
                 if (rc) return rc;
@@ -323,7 +323,7 @@ static int plan5_sweeps(const Problem &p, const xinv_options &opt, Workspace *, 
         pl.K = 2;
         for (int k = ksup; k > 2; k--) {                 // (pl.pipe, pl.pq, pl.alias_ac are still unset: the plain k_fused2d variant)
             bool have = false;
-            if (plan_occ(p, pl, st, k, &have) >= occ_needed && have) { pl.K = k; break; }
+            if (plan_occ(p, pl, k, &have) >= occ_needed && have) { pl.K = k; break; }
         }
     }
     pl.pipe = pipe_want && pl.K == XINV_PIPE_P;
@@ -378,7 +378,7 @@ static int plan5_row_records(const Problem &p, const xinv_options &, Workspace *
     ra.yc = p.yc; ra.xc = p.xc; ra.sc_ = p.sc_; ra.rowf = (double *)ws->d_rowf;
     hipLaunchKernelGGL(k_row_factor, dim3(cdiv(p.yc, 256), (unsigned)p.nbatch, 1), dim3(256), 0, st, ra);
     // the march's update masks: the row predicate just written, the launch's lane -> column map, the forcing's mask
-    const int nstrip = (int)cdiv(p.xc, strip_uw(pl, pl.K, true));
+    const int nstrip = (int)cdiv(p.xc, own_cols(p, pl, pl.K, true));
     const int rc2 = ensure_dev(&ws->d_pmask, &ws->d_pmask_cap,
                                (size_t)xinv_pipe_mask_count(p.nbatch, nstrip, p.yc) * sizeof(unsigned long long));
     if (rc2) return rc2;
@@ -395,12 +395,12 @@ static int plan5_row_split(const Problem &p, const xinv_options &opt, Workspace 
     // (register-limited), so the target is a multiple of 512 workgroups.  Pick the row-block
     // count that minimises (workgroups per CU) x (steps per tile); rows are then split
     // evenly (measured at 3600x1800: 64 blocks of ~28 rows beat 53 blocks of 34).
-    const int occ = plan_occ(p, pl, st, pl.K);         // workgroups of the chosen variant per CU
+    const int occ = plan_occ(p, pl, pl.K);         // workgroups of the chosen variant per CU
     // (pl.lone, set with K above: with one or two vector streams a second workgroup per CU
     // fills idle issue slots; with four or more a pair runs no faster than one, and tall
     // tiles (less halo) win -- 2000x2000 general form, A C G streamed: 40-row tiles 38.3 us,
     // 17-row tiles 44.0 us)
-    split_rows_evenly(p, pl, choose_row_blocks(p.yc, cdiv(p.xc, strip_uw(pl, pl.K, pl.pipe)), p.nbatch, pl.K, occ, pl.lone, pl.pipe));
+    split_rows_evenly(p, pl, choose_row_blocks(p.yc, cdiv(p.xc, own_cols(p, pl, pl.K, pl.pipe)), p.nbatch, pl.K, occ, pl.lone, pl.pipe));
     return XINV_OK;
 }
 
@@ -408,8 +408,8 @@ static int plan5_row_split(const Problem &p, const xinv_options &opt, Workspace 
 // (the shorter tail / redo passes of a pipelined plan run k_fused2d: four 112-column tiles per workgroup)
 static int plan5_partials(const Problem &p, const xinv_options &, Workspace *, hipStream_t, Plan &pl)
 {
-    pl.nsg = (int)cdiv((int64_t)cdiv(p.xc, strip_uw(pl, XINV_KMAX, false)) * pl.nrb, 4) + 1;
-    if (pl.pipe) pl.nsg = std::max(pl.nsg, (int)cdiv(p.xc, strip_uw(pl, pl.K, true)) * pl.nrb + 1);
+    pl.nsg = (int)cdiv((int64_t)cdiv(p.xc, own_cols(p, pl, XINV_KMAX, false)) * pl.nrb, 4) + 1;
+    if (pl.pipe) pl.nsg = std::max(pl.nsg, (int)cdiv(p.xc, own_cols(p, pl, pl.K, true)) * pl.nrb + 1);
     return XINV_OK;
 }
 
@@ -425,6 +425,21 @@ static int plan_fused5(const Problem &p, const xinv_options &opt, Workspace *ws,
         if (rc) return rc;
     }
     return plan_pipe_tile_recs(p, pl, ws, st);           // (no tile skipped: the pipelined pass's records of the final split)
+}
+
+// The kernel of every pass length the sweep loops can ask a fused plan for: k = 1 .. pl.K (plan_variant).  A variant no
+// unit instantiates fails the plan here (the planner's own caps on K and the cross-section keep a planned solve away from it).
+static int plan_kernels(const Problem &p, Plan &pl)
+{
+    for (int k = 1; k <= pl.K; k++) {
+        pl.kern[k] = xinv_kernel(plan_variant(p, pl, k));
+        if (pl.kern[k].fn) continue;
+        return fail_arg(p.kind == KIND_GEN3D ? "internal: no general 3-D kernel variant for this cross-section"
+                      : p.kind == KIND_STD3D ? "internal: no 3-D kernel variant for this cross-section"
+                      : pl.nine              ? "unsupported sweeps_per_launch for the 9-point kernel"
+                                             : "unsupported sweeps_per_launch for this kernel variant");
+    }
+    return XINV_OK;
 }
 
 // which path, then the tiling of its kernel family

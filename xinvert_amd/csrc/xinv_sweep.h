@@ -34,18 +34,16 @@ struct SweepRun {
 };
 #define XINV_MAX_LAUNCH_EVENTS 8192
 
-// one sweep launch of the planned kernel (fused: k sweeps from src into dst; colour path: one sweep in place)
-static int launch_planned(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t s, int k,
-                          const double *src, double *dst, int64_t member0, int64_t nmem, int force, int no_ctl,
-                          unsigned lag_tag = 0, NormLagArgs *lag_out = nullptr, const NormLagArgs *lag_prev = nullptr,
-                          bool prepass = true)
+// one sweep launch of the planned kernel (SweepLaunch; fused: k sweeps from src into dst; colour path: one sweep in place)
+static int launch_planned(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t s, const SweepLaunch &L)
 {
     if (pl.path != XINV_PATH_FUSED) return launch_colour_sweep(p, pl, ws, s);
-    return (p.kind == KIND_BIH2D)   ? launch_fusedbih(p, pl, src, dst, ws, s, member0, nmem, force, no_ctl, lag_tag, lag_out, lag_prev, prepass)
-         : (p.kind == KIND_GEN3D)   ? launch_fused3dg(p, pl, src, dst, ws, s, member0, nmem, force, no_ctl)
-         : (p.kind == KIND_STD3D)   ? launch_fused3d(p, pl, k, src, dst, ws, s, member0, nmem, force, no_ctl)
-         : pl.nine                  ? launch_fused9(p, pl, k, src, dst, ws, s, member0, nmem, force, no_ctl, lag_tag, lag_out, lag_prev)
-                                    : launch_fused(p, pl, k, src, dst, ws, s, member0, nmem, force, no_ctl, lag_tag, lag_out, lag_prev);
+    if (L.k < 1 || L.k > pl.K) return fail_arg("internal: a pass length the plan holds no kernel for");
+    return (p.kind == KIND_BIH2D)   ? launch_fusedbih(p, pl, ws, s, L)
+         : (p.kind == KIND_GEN3D)   ? launch_fused3dg(p, pl, ws, s, L)
+         : (p.kind == KIND_STD3D)   ? launch_fused3d(p, pl, ws, s, L)
+         : pl.nine                  ? launch_fused9(p, pl, ws, s, L)
+                                    : launch_fused(p, pl, ws, s, L);
 }
 
 // sweep loop in lanes (run_sweeps): how many independent launch chains the batch is cut into.
@@ -156,11 +154,10 @@ static bool lag_candidate(const Problem &p, const Plan &pl, const xinv_options &
     const bool lag_env = opt.norm_lag ? opt.norm_lag > 0 : XINV_ENV_INT("XINV_LAG", 1) != 0;
     // Only where a member has many workgroups: the reducing workgroup is one more per member and launch,
     // and with one or two tile workgroups per member (365 slices of 73x144) it would double the launch.
-    const int64_t own_cols = (p.kind == KIND_BIH2D) ? XINV_BIH_OWN(p.BCx == XINV_BC_PERIODIC)
-                           : (pl.path == XINV_PATH_FUSED && pl.pipe) ? strip_uw(pl, pl.K, true)
-                                                    : (pl.nine ? strip9_uw(pl, std::max(1, pl.K)) : strip_uw(pl, std::max(1, pl.K), false));
-    const int tpw = (pl.path == XINV_PATH_FUSED && pl.pipe) ? 1 : 4;
-    const int64_t wg_member = pl.skip ? pl.ntl / tpw : (int64_t)cdiv((int64_t)cdiv(p.xc, own_cols) * pl.nrb, tpw);
+    const bool pipe = pl.path == XINV_PATH_FUSED && pl.pipe;
+    const int tpw = pipe ? 1 : 4;
+    const int64_t wg_member = pl.skip ? pl.ntl / tpw
+                                      : (int64_t)cdiv((int64_t)cdiv(p.xc, own_cols(p, pl, std::max(1, pl.K), pipe)) * pl.nrb, tpw);
     // ... and only where a launch is one or two rounds of workgroups: with many rounds (64 Gill-Matsuno
     // members: 3.97e11 without, 3.73e11 with) the in-kernel reducer's wait already hides behind other tiles.
     return lag_env && pl.path == XINV_PATH_FUSED && wg_member >= 32 &&
@@ -206,7 +203,7 @@ static int capture_chunk(const Problem &p, const Plan &pl, const xinv_options &o
     if (hipStreamBeginCapture(ws->gstream, hipStreamCaptureModeRelaxed) == hipSuccess) {
         int r = XINV_OK;
         for (int i = 0; i < check_every && r == XINV_OK; i++)
-            r = launch_planned(p, pl, ws, ws->gstream, R.Kf, R.buf[i & 1], R.buf[(i & 1) ^ 1], 0, p.nbatch, 0, 0);
+            r = launch_planned(p, pl, ws, ws->gstream, SweepLaunch{R.Kf, R.buf[i & 1], R.buf[(i & 1) ^ 1], 0, p.nbatch});
         const hipError_t ce = hipStreamEndCapture(ws->gstream, &g);
         if (!(r == XINV_OK && ce == hipSuccess && g && hipGraphInstantiate(&R.graph_exec, g, nullptr, nullptr, 0) == hipSuccess))
             R.graph_exec = nullptr;
@@ -286,7 +283,9 @@ static int recover_member(const Problem &p, const Plan &pl, Workspace *ws, hipSt
             //  XINV_EXP_WATCHDOG stops the member BEFORE that launch: no hooks case combines it with this form.)
             const bool prepass = !(s == L && p.kind == KIND_BIH2D && p.BCy == XINV_BC_EXTEND);
             double *dst = R.buf[xinv_redo_write(r, s - L)];
-            if ((rc = launch_planned(p, pl, ws, st, 1, R.buf[xinv_redo_read(r, s - L)], dst, m, 1, 0, 1, 0, nullptr, nullptr, prepass))) return rc;
+            SweepLaunch one{1, R.buf[xinv_redo_read(r, s - L)], dst, m, 1};
+            one.no_ctl = 1; one.prepass = prepass;
+            if ((rc = launch_planned(p, pl, ws, st, one))) return rc;
             na.S = dst;
             hipLaunchKernelGGL(k_norm_partial, dim3(nblk, 1, 1), dim3(256, 1, 1), 0, st, na);
             hipLaunchKernelGGL(k_norm_final, dim3(1, 1, 1), dim3(64, 1, 1), 0, st, na, nblk);
@@ -444,8 +443,9 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
             hipStream_t sl = l ? ws->s_lane[l] : st;
             const int64_t m0 = lane_first(l), nm = lane_first(l + 1) - m0;
             NormLagArgs la;
-            const int r = lag ? launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0, (unsigned)(i + 1), &la, &lag_pending[l])
-                              : launch_planned(p, pl, ws, sl, k, src, dst, m0, nm, 0, 0);
+            SweepLaunch pass{k, src, dst, m0, nm};
+            if (lag) { pass.lag_tag = (unsigned)(i + 1); pass.lag_out = &la; pass.lag_prev = &lag_pending[l]; }
+            const int r = launch_planned(p, pl, ws, sl, pass);
             if (r) return r;
             if (lag) lag_pending[l] = la;                // evaluated by the lane's next launch, or by flush_lag()
         }
@@ -493,7 +493,7 @@ static int run_sweeps(const Problem &p, const Plan &pl, const xinv_options &opt,
                 bound.push_back(launched);
                 launched += k;
             } else {
-                r = launch_planned(p, pl, ws, st, 1, buf[0], buf[1], 0, p.nbatch, 0, 0);
+                r = launch_planned(p, pl, ws, st, SweepLaunch{1, buf[0], buf[1], 0, p.nbatch});
                 if (r) return r;
                 launched += 1;
             }
@@ -601,8 +601,9 @@ static int finalise(const Problem &p, const Plan &pl, Workspace *ws, hipStream_t
                                                extend_lag, hc[m].sweeps);
                 if (w.launch < 0) { t_err = "internal: final sweep outside the launches issued"; return XINV_ERR_HIP; }
                 for (int64_t q = 0; q < w.f.redo; q++) {     // stopped inside a K-sweep launch: redo from its source
-                    if (int rc = launch_planned(p, pl, ws, st, 1, buf[xinv_redo_read(w.f.r, q)], buf[xinv_redo_write(w.f.r, q)],
-                                                m, 1, 1, 1, 0, nullptr, nullptr, !w.hit)) return rc;
+                    SweepLaunch one{1, buf[xinv_redo_read(w.f.r, q)], buf[xinv_redo_write(w.f.r, q)], m, 1};
+                    one.force = one.no_ctl = 1; one.prepass = !w.hit;
+                    if (int rc = launch_planned(p, pl, ws, st, one)) return rc;
                 }
                 where = w.f.where;
             }
@@ -688,7 +689,7 @@ static int make_plan(const Problem &p, const xinv_options &opt, Workspace *ws, h
                             "variants only (standard 2-D with A, C constant along x; general 2-D with A, C, D, E, F constant "
                             "along x; standard 3-D with A, B, C constant along x; B == 0; no odd-xc periodic seam)");
     }
-    return XINV_OK;
+    return pl.path == XINV_PATH_FUSED ? plan_kernels(p, pl) : XINV_OK;
 }
 
 static int solve_dev(Problem &p, double *flags, const xinv_options *opt_in, hipStream_t st, int slot = 0)
@@ -964,7 +965,7 @@ static int plan_solve_frames(xinv_plan *h, double *S, double *frames, int64_t nf
             solve_init(ws, st, nb, ws->partials_half);
             for (int64_t i = 0; i < L; i++) {
                 const int k = (int)std::min<int64_t>(Kf, max_sweeps - i * Kf);
-                rc = launch_planned(p, pl, ws, st, k, buf[cur], buf[cur ^ 1], 0, nb, 0, 0);
+                rc = launch_planned(p, pl, ws, st, SweepLaunch{k, buf[cur], buf[cur ^ 1], 0, nb});
                 if (rc) return rc;
                 cur ^= 1; nlaunch++;
             }

@@ -4,29 +4,17 @@
 // vm: 0 = A..I per row (records); 1 = A, C, D, F vector streams (B == E == 0: zbe); 3 = ... with C read out of A, F out of D;
 //     2 = all nine vector streams
 template <int VM>
-static int launch_vm(bool per, bool zbe, dim3 grid, hipStream_t st, const FusedBihArgs &a, int *occ)
+static KernelRef bih_vm(bool per, bool zbe)
 {
-    if (occ) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fusedbih<false, VM == 1 || VM == 3, VM>, 256, 0) != hipSuccess || n < 1) n = 1;
-        *occ = n;
-        return 0;
-    }
-    dim3 block(256, 1, 1);
-    if (zbe || VM == 1 || VM == 3) {
-        if (per) hipLaunchKernelGGL((k_fusedbih<true, true, VM>), grid, block, 0, st, a);
-        else     hipLaunchKernelGGL((k_fusedbih<false, true, VM>), grid, block, 0, st, a);
-    } else if constexpr (VM != 1 && VM != 3) {
-        if (per) hipLaunchKernelGGL((k_fusedbih<true, false, VM>), grid, block, 0, st, a);
-        else     hipLaunchKernelGGL((k_fusedbih<false, false, VM>), grid, block, 0, st, a);
-    }
-    return 0;
+    if constexpr (VM != 1 && VM != 3)
+        if (!zbe) return per ? kernel_ref(k_fusedbih<true, false, VM>, 256) : kernel_ref(k_fusedbih<false, false, VM>, 256);
+    return per ? kernel_ref(k_fusedbih<true, true, VM>, 256) : kernel_ref(k_fusedbih<false, true, VM>, 256);
 }
 
-int xinv_launch_fusedbih(bool per, bool zbe, int vm, dim3 grid, hipStream_t st, const FusedBihArgs &a, int *occ)
+KernelRef xinv_kernel_bih(const SweepVariant &v)
 {
-    if (vm == 1) return launch_vm<1>(per, true, grid, st, a, occ);
-    if (vm == 3) return launch_vm<3>(per, true, grid, st, a, occ);
-    if (vm == 2) return launch_vm<2>(per, zbe, grid, st, a, occ);
-    return launch_vm<0>(per, zbe, grid, st, a, occ);
+    if (v.vm == 1) return bih_vm<1>(v.per, v.zbe);
+    if (v.vm == 3) return bih_vm<3>(v.per, v.zbe);
+    if (v.vm == 2) return bih_vm<2>(v.per, v.zbe);
+    return bih_vm<0>(v.per, v.zbe);
 }

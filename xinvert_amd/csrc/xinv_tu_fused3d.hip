@@ -2,55 +2,36 @@
 // coefficients).  k_pipe3d (two sweeps per pass) has its own unit, xinv_tu_pipe3d.hip.
 #include "xinv_dispatch.h"
 
-// ---- 3-D fused launch ------------------------------------------------------------------------
+template <int NW, bool AL>
+static KernelRef fused3d_uni_ext(bool uni, bool ext)
+{
+    if (uni) return ext ? kernel_ref(k_fused3d<NW, AL, true, true>, NW * 64) : kernel_ref(k_fused3d<NW, AL, true, false>, NW * 64);
+    return ext ? kernel_ref(k_fused3d<NW, AL, false, true>, NW * 64) : kernel_ref(k_fused3d<NW, AL, false, false>, NW * 64);
+}
+
+static KernelRef fused3d(const SweepVariant &v)
+{
+    if (v.NW == 8) return v.al ? fused3d_uni_ext<8, true>(v.uni, v.ext) : fused3d_uni_ext<8, false>(v.uni, v.ext);
+    if (v.NW == 12) return v.al ? fused3d_uni_ext<12, true>(v.uni, v.ext) : fused3d_uni_ext<12, false>(v.uni, v.ext);
+    // sixteen wavefronts leave 128 VGPRs per lane: enough for the x-uniform variant without 'extend' only (the other
+    // sixteen-wavefront variants spilled 76-203 bytes per lane and are not instantiated: the planner gives them twelve)
+    if (v.NW == 16 && v.uni && !v.ext)
+        return v.al ? kernel_ref(k_fused3d<16, true, true, false>, 16 * 64) : kernel_ref(k_fused3d<16, false, true, false>, 16 * 64);
+    return KernelRef{};
+}
+
+// general 3-D form (every coefficient array x-uniform; sixteen wavefronts: 128 VGPRs, spills -- not instantiated)
 template <int NW>
-static int launch_fused3d_nw(bool al, bool uni, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+static KernelRef fused3dg_nw(bool al, bool ext)
 {
-    dim3 block(NW * 64, 1, 1);
-#define L3(AL, UNI, EXT) hipLaunchKernelGGL((k_fused3d<NW, AL, UNI, EXT>), grid, block, 0, st, a)
-    if (al) {
-        if (uni) { if (ext) L3(true, true, true); else L3(true, true, false); }
-        else     { if (ext) L3(true, false, true); else L3(true, false, false); }
-    } else {
-        if (uni) { if (ext) L3(false, true, true); else L3(false, true, false); }
-        else     { if (ext) L3(false, false, true); else L3(false, false, false); }
-    }
-#undef L3
-    return 0;
+    if (al) return ext ? kernel_ref(k_fused3dg<NW, true, true>, NW * 64) : kernel_ref(k_fused3dg<NW, true, false>, NW * 64);
+    return ext ? kernel_ref(k_fused3dg<NW, false, true>, NW * 64) : kernel_ref(k_fused3dg<NW, false, false>, NW * 64);
 }
 
-
-int xinv_launch_fused3d(int NW, bool al, bool uni, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+KernelRef xinv_kernel_fused3d(const SweepVariant &v)
 {
-    if (NW == 8) return launch_fused3d_nw<8>(al, uni, ext, grid, st, a);
-    if (NW == 16 && uni && !ext) {
-        // sixteen wavefronts leave 128 VGPRs per lane: enough for the x-uniform variant without 'extend' only (the
-        // other sixteen-wavefront variants spilled 76-203 bytes per lane and are not instantiated: the planner
-        // gives them twelve)
-        if (al) hipLaunchKernelGGL((k_fused3d<16, true, true, false>), grid, dim3(16 * 64, 1, 1), 0, st, a);
-        else    hipLaunchKernelGGL((k_fused3d<16, false, true, false>), grid, dim3(16 * 64, 1, 1), 0, st, a);
-        return 0;
-    }
-    if (NW != 12) return 1;
-    return launch_fused3d_nw<12>(al, uni, ext, grid, st, a);
-}
-
-// ---- general 3-D fused launch (every coefficient array x-uniform) --------------------------------
-template <int NW>
-static void launch_fused3dg_nw(bool al, bool ext, dim3 grid, hipStream_t st, const Fused3GArgs &a)
-{
-    dim3 block(NW * 64, 1, 1);
-    if (al) { if (ext) hipLaunchKernelGGL((k_fused3dg<NW, true, true>), grid, block, 0, st, a);
-              else     hipLaunchKernelGGL((k_fused3dg<NW, true, false>), grid, block, 0, st, a); }
-    else    { if (ext) hipLaunchKernelGGL((k_fused3dg<NW, false, true>), grid, block, 0, st, a);
-              else     hipLaunchKernelGGL((k_fused3dg<NW, false, false>), grid, block, 0, st, a); }
-}
-
-
-int xinv_launch_fused3dg(int NW, bool al, bool ext, dim3 grid, hipStream_t st, const Fused3GArgs &a)
-{
-    if (NW == 8) launch_fused3dg_nw<8>(al, ext, grid, st, a);      // (sixteen wavefronts: 128 VGPRs, spills -- not instantiated)
-    else if (NW == 12) launch_fused3dg_nw<12>(al, ext, grid, st, a);
-    else return 1;
-    return 0;
+    if (v.family == FAM_FUSED3D) return fused3d(v);
+    if (v.NW == 8) return fused3dg_nw<8>(v.al, v.ext);
+    if (v.NW == 12) return fused3dg_nw<12>(v.al, v.ext);
+    return KernelRef{};
 }

@@ -3,24 +3,17 @@
 #include "xinv_dispatch.h"
 
 template <int NW>
-static int launch_fused3d_fma_nw(bool al, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+static KernelRef fused3d_fma_nw(bool al, bool ext)
 {
-    dim3 block(NW * 64, 1, 1);
-    if (al) { if (ext) hipLaunchKernelGGL((k_fused3d<NW, true, true, true, true>), grid, block, 0, st, a);
-              else     hipLaunchKernelGGL((k_fused3d<NW, true, true, false, true>), grid, block, 0, st, a); }
-    else    { if (ext) hipLaunchKernelGGL((k_fused3d<NW, false, true, true, true>), grid, block, 0, st, a);
-              else     hipLaunchKernelGGL((k_fused3d<NW, false, true, false, true>), grid, block, 0, st, a); }
-    return 0;
+    if (al) return ext ? kernel_ref(k_fused3d<NW, true, true, true, true>, NW * 64) : kernel_ref(k_fused3d<NW, true, true, false, true>, NW * 64);
+    return ext ? kernel_ref(k_fused3d<NW, false, true, true, true>, NW * 64) : kernel_ref(k_fused3d<NW, false, true, false, true>, NW * 64);
 }
 
-int xinv_launch_fused3d_fma(int NW, bool al, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+KernelRef xinv_kernel_fused3d_fma(const SweepVariant &v)
 {
-    if (NW == 8) return launch_fused3d_fma_nw<8>(al, ext, grid, st, a);
-    if (NW == 16 && !ext) {                              // (as the plain kernel: sixteen wavefronts without 'extend' only)
-        if (al) hipLaunchKernelGGL((k_fused3d<16, true, true, false, true>), grid, dim3(16 * 64, 1, 1), 0, st, a);
-        else    hipLaunchKernelGGL((k_fused3d<16, false, true, false, true>), grid, dim3(16 * 64, 1, 1), 0, st, a);
-        return 0;
-    }
-    if (NW != 12) return 1;
-    return launch_fused3d_fma_nw<12>(al, ext, grid, st, a);
+    if (v.NW == 8) return fused3d_fma_nw<8>(v.al, v.ext);
+    if (v.NW == 12) return fused3d_fma_nw<12>(v.al, v.ext);
+    if (v.NW == 16 && !v.ext)                            // (as the plain kernel: sixteen wavefronts without 'extend' only)
+        return v.al ? kernel_ref(k_fused3d<16, true, true, false, true>, 16 * 64) : kernel_ref(k_fused3d<16, false, true, false, true>, 16 * 64);
+    return KernelRef{};
 }

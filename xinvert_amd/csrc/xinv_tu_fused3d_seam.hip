@@ -1,38 +1,19 @@
 // xinv_tu_fused3d_seam.hip -- k_fused3d / k_fused3dg with the odd-xc periodic seam inside the kernel (SEAM variants: unaligned strips,
-// the even-ring layout; xinv_fused3d.h).
+// the even-ring layout; xinv_fused3d.h), eight or twelve wavefronts.
 #include "xinv_dispatch.h"
 
 template <int NW>
-static int launch_fused3d_seam_nw(bool uni, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+static KernelRef seam_nw(const SweepVariant &v)
 {
-    dim3 block(NW * 64, 1, 1);
-#define L3(UNI, EXT) hipLaunchKernelGGL((k_fused3d<NW, false, UNI, EXT, false, true>), grid, block, 0, st, a)
-    if (uni) { if (ext) L3(true, true); else L3(true, false); }
-    else     { if (ext) L3(false, true); else L3(false, false); }
-#undef L3
-    return 0;
+    if (v.family == FAM_FUSED3DG)                        // general 3-D form (x-uniform coefficients)
+        return v.ext ? kernel_ref(k_fused3dg<NW, false, true, true>, NW * 64) : kernel_ref(k_fused3dg<NW, false, false, true>, NW * 64);
+    if (v.uni) return v.ext ? kernel_ref(k_fused3d<NW, false, true, true, false, true>, NW * 64) : kernel_ref(k_fused3d<NW, false, true, false, false, true>, NW * 64);
+    return v.ext ? kernel_ref(k_fused3d<NW, false, false, true, false, true>, NW * 64) : kernel_ref(k_fused3d<NW, false, false, false, false, true>, NW * 64);
 }
 
-int xinv_launch_fused3d_seam(int NW, bool uni, bool ext, dim3 grid, hipStream_t st, const Fused3Args &a)
+KernelRef xinv_kernel_fused3d_seam(const SweepVariant &v)
 {
-    if (NW == 8) return launch_fused3d_seam_nw<8>(uni, ext, grid, st, a);
-    if (NW == 12) return launch_fused3d_seam_nw<12>(uni, ext, grid, st, a);
-    return 1;
-}
-
-// general 3-D form (x-uniform coefficients)
-template <int NW>
-static void launch_fused3dg_seam_nw(bool ext, dim3 grid, hipStream_t st, const Fused3GArgs &a)
-{
-    dim3 block(NW * 64, 1, 1);
-    if (ext) hipLaunchKernelGGL((k_fused3dg<NW, false, true, true>), grid, block, 0, st, a);
-    else     hipLaunchKernelGGL((k_fused3dg<NW, false, false, true>), grid, block, 0, st, a);
-}
-
-int xinv_launch_fused3dg_seam(int NW, bool ext, dim3 grid, hipStream_t st, const Fused3GArgs &a)
-{
-    if (NW == 8) launch_fused3dg_seam_nw<8>(ext, grid, st, a);
-    else if (NW == 12) launch_fused3dg_seam_nw<12>(ext, grid, st, a);
-    else return 1;
-    return 0;
+    if (v.NW == 8) return seam_nw<8>(v);
+    if (v.NW == 12) return seam_nw<12>(v);
+    return KernelRef{};
 }

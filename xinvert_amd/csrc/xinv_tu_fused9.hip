@@ -2,38 +2,24 @@
 #include "xinv_dispatch.h"
 #include "xinv_fused9.h"
 
-// ---- 9-point fused launch ---------------------------------------------------------------------
 template <class M, int K>
-static void launch_fused9_k(bool al, bool ext, bool seam, dim3 grid, hipStream_t st, const FusedArgs &a, int *occ)
+static KernelRef fused9_k(const SweepVariant &v)
 {
-    dim3 block(256, 1, 1);
-#define L9(AL, EXT, SEAM)                                                                        \
-    do {                                                                                         \
-        if (occ) {                                                                               \
-            int n = 0;                                                                           \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fused9<M, K, AL, EXT, SEAM>, 256, 0) != hipSuccess) n = 1; \
-            *occ = n < 1 ? 1 : n;                                                                \
-        } else hipLaunchKernelGGL((k_fused9<M, K, AL, EXT, SEAM>), grid, block, 0, st, a);       \
-    } while (0)
-    if (seam) { if (ext) L9(false, true, true); else L9(false, false, true); }     // (odd xc: unaligned strips)
-    else if (al) { if (ext) L9(true, true, false); else L9(true, false, false); }
-    else    { if (ext) L9(false, true, false); else L9(false, false, false); }
-#undef L9
+    if (v.seam)                                          // (odd xc: unaligned strips)
+        return v.ext ? kernel_ref(k_fused9<M, K, false, true, true>, 256) : kernel_ref(k_fused9<M, K, false, false, true>, 256);
+    if (v.al) return v.ext ? kernel_ref(k_fused9<M, K, true, true, false>, 256) : kernel_ref(k_fused9<M, K, true, false, false>, 256);
+    return v.ext ? kernel_ref(k_fused9<M, K, false, true, false>, 256) : kernel_ref(k_fused9<M, K, false, false, false>, 256);
 }
 
-int xinv_launch_fused9(bool gen, int K, bool al, bool ext, dim3 grid, hipStream_t st,
-                       const FusedArgs &a, int *occ, bool seam)
+KernelRef xinv_kernel_fused9(const SweepVariant &v)
 {
-    if (gen) {
-        if (K == 1) launch_fused9_k<Fused9Gen, 1>(al, ext, seam, grid, st, a, occ);
-        else if (K == 2) launch_fused9_k<Fused9Gen, 2>(al, ext, seam, grid, st, a, occ);
-        else return 1;
+    if (v.kind == KIND_GEN2D) {
+        if (v.K == 1) return fused9_k<Fused9Gen, 1>(v);
+        if (v.K == 2) return fused9_k<Fused9Gen, 2>(v);
     } else {
-        if (K == 1) launch_fused9_k<Fused9Std, 1>(al, ext, seam, grid, st, a, occ);
-        else if (K == 2) launch_fused9_k<Fused9Std, 2>(al, ext, seam, grid, st, a, occ);
-        else if (K == 3) launch_fused9_k<Fused9Std, 3>(al, ext, seam, grid, st, a, occ);
-        else return 1;
+        if (v.K == 1) return fused9_k<Fused9Std, 1>(v);
+        if (v.K == 2) return fused9_k<Fused9Std, 2>(v);
+        if (v.K == 3) return fused9_k<Fused9Std, 3>(v);
     }
-    return 0;
+    return KernelRef{};
 }
-

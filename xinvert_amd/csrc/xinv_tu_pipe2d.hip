@@ -1,6 +1,8 @@
-// xinv_tu_pipe2d.hip -- instantiations of k_pipe2d (wave-pipelined four-sweep pass, xinv_pipe2d.h) for ONE model
-// (compiled twice: -DXINV_TU_MODEL=0 standard form, 1 general form; each once more with -DXINV_TU_SEAM=1: the odd-xc
-// periodic seam variants -- unaligned strips).
+// xinv_tu_pipe2d.hip -- instantiations of k_pipe2d (wave-pipelined four-sweep pass, one tile per 256-thread workgroup:
+// xinv_pipe2d.h) for ONE model (-DXINV_TU_MODEL=0 standard form, um = 3: A and C per row; 1 general form, um = 0x1f: A C D
+// E F per row; each once more with -DXINV_TU_SEAM=1: the odd-xc periodic seam variants -- unaligned strips; 2: both forms
+// in contracted arithmetic, XINV_FLAG_FMA).  No variant for coefficient arrays that vary along x: measured slower than
+// k_fused2d (plan5_sweeps).
 #include "xinv_dispatch.h"
 
 #ifndef XINV_TU_SEAM
@@ -8,58 +10,31 @@
 #endif
 constexpr bool SEAM = XINV_TU_SEAM != 0;
 
-template <class M, unsigned UM, bool FR, bool AL, bool EXT>
-static int pipe_one(dim3 grid, hipStream_t st, const FusedArgs &a, int *occ, int lds_pad)
-{
-    if (occ) {
-        static int cached = 0;                           // (asked by the planner in every solve: a few microseconds per query)
-        int n = cached;
-        if (!n) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_pipe2d<M, UM, FR, AL, EXT, SEAM>, 64 * XINV_PIPE_P, 0) != hipSuccess)
-                n = 1;
-            cached = n = n < 1 ? 1 : n;
-        }
-        *occ = n;
-        return 0;
-    }
-    hipLaunchKernelGGL((k_pipe2d<M, UM, FR, AL, EXT, SEAM>), grid, dim3(64 * XINV_PIPE_P, 1, 1), (size_t)lds_pad, st, a);
-    return 0;
-}
-
 template <class M, unsigned UM, bool FR>
-static int pipe_variant(bool al, bool ext, dim3 grid, hipStream_t st, const FusedArgs &a, int *occ, int lds_pad)
+static KernelRef pipe_al_ext(bool al, bool ext)
 {
+    constexpr unsigned T = 64 * XINV_PIPE_P;
     if constexpr (!SEAM) {
-        if (al) return ext ? pipe_one<M, UM, FR, true, true>(grid, st, a, occ, lds_pad) : pipe_one<M, UM, FR, true, false>(grid, st, a, occ, lds_pad);
-    } else if (al) return 1;
-    return ext ? pipe_one<M, UM, FR, false, true>(grid, st, a, occ, lds_pad) : pipe_one<M, UM, FR, false, false>(grid, st, a, occ, lds_pad);
+        if (al) return ext ? kernel_ref(k_pipe2d<M, UM, FR, true, true, SEAM>, T) : kernel_ref(k_pipe2d<M, UM, FR, true, false, SEAM>, T);
+    } else if (al) return KernelRef{};
+    return ext ? kernel_ref(k_pipe2d<M, UM, FR, false, true, SEAM>, T) : kernel_ref(k_pipe2d<M, UM, FR, false, false, SEAM>, T);
 }
 
-#if XINV_TU_SEAM
-#define xinv_launch_pipe2d_std xinv_launch_pipe2d_std_seam
-#define xinv_launch_pipe2d_gen xinv_launch_pipe2d_gen_seam
+// pipe_fr: the forcing row rides the LDS ring with S
+template <class M, unsigned UM>
+static KernelRef pipe_m(const SweepVariant &v)
+{
+    if (v.um != UM) return KernelRef{};
+    return v.pipe_fr ? pipe_al_ext<M, UM, true>(v.al, v.ext) : pipe_al_ext<M, UM, false>(v.al, v.ext);
+}
+
+template <> XINV_HIDDEN KernelRef xinv_kernel_pipe2d<XINV_TU_MODEL, SEAM>(const SweepVariant &v)
+{
+#if XINV_TU_MODEL == 2       /* PIPE2D_FMA */
+    return v.kind == KIND_GEN2D ? pipe_m<FusedGen2DF, 0x1fu>(v) : pipe_m<FusedStd2DF, 3u>(v);
+#elif XINV_TU_MODEL == 0     /* PIPE2D_STD */
+    return pipe_m<FusedStd2D, 3u>(v);
+#else                        /* PIPE2D_GEN */
+    return pipe_m<FusedGen2D, 0x1fu>(v);
 #endif
-#if XINV_TU_MODEL == 2        /* contracted arithmetic (XINV_FLAG_FMA), both forms in one unit */
-int xinv_launch_pipe2d_fma(bool gen, unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st, const FusedArgs &a, int *occ, int lds_pad)
-{
-    if (!gen && um == 3u) return fr ? pipe_variant<FusedStd2DF, 3u, true>(al, ext, grid, st, a, occ, lds_pad)
-                                    : pipe_variant<FusedStd2DF, 3u, false>(al, ext, grid, st, a, occ, lds_pad);
-    if (gen && um == 0x1fu) return fr ? pipe_variant<FusedGen2DF, 0x1fu, true>(al, ext, grid, st, a, occ, lds_pad)
-                                      : pipe_variant<FusedGen2DF, 0x1fu, false>(al, ext, grid, st, a, occ, lds_pad);
-    return 1;
 }
-#elif XINV_TU_MODEL == 0
-int xinv_launch_pipe2d_std(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st, const FusedArgs &a, int *occ, int lds_pad)
-{
-    if (um == 3u) return fr ? pipe_variant<FusedStd2D, 3u, true>(al, ext, grid, st, a, occ, lds_pad)
-                            : pipe_variant<FusedStd2D, 3u, false>(al, ext, grid, st, a, occ, lds_pad);
-    return 1;
-}
-#else
-int xinv_launch_pipe2d_gen(unsigned um, bool fr, bool al, bool ext, dim3 grid, hipStream_t st, const FusedArgs &a, int *occ, int lds_pad)
-{
-    if (um == 0x1fu) return fr ? pipe_variant<FusedGen2D, 0x1fu, true>(al, ext, grid, st, a, occ, lds_pad)
-                               : pipe_variant<FusedGen2D, 0x1fu, false>(al, ext, grid, st, a, occ, lds_pad);
-    return 1;
-}
-#endif
